@@ -6,7 +6,27 @@ T_cleanup sweep, k=4 Philox-peer max-merge) over the N x N int32 heartbeat and
 timestamp tables resident in HBM (BASELINE config 3, SURVEY.md §8d C3:
 full membership hb=2 ts=0, seed 0x5EED0003).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets the engine up, runs W warm-up rounds, times K rounds in one
+gh_step call, writes its outputs if --dump-outputs is given and prints the
+JSON line: the headline value, ms_per_step and the k_round roofline (HIP
+events of the timed rounds themselves). Every other leg (cpu_baseline,
+secondary, placement and election; below) runs only with --full, after the
+timed rounds; without it those keys are null.
+
+--dump-outputs DIR writes what the timed gh_step call left its caller, after
+the last timed round, as float64 .npy files (the inputs are the same from run
+to run: init_full and the seed):
+  round_stats.npy  the call's gh_round_stats, in the struct's field order
+                   (rounds, last_round, detections, failed_members,
+                   remove_unknown, ring_empty, active_rows, merged_cells,
+                   released, tombstoned)
+  rows.npy         the observer rows sampled (a fixed seeded draw, ascending;
+                   every row while two N x N float64 tables fit in 48 MB)
+  hb_rows.npy      gh_export_state's heartbeat table, rows `rows` x all N columns
+  ts_rows.npy      its timestamp table, the same rows
+  alive.npy        its alive vector, all N members
 
 N>1 is launched by the driver under torch.distributed.run, one rank per GPU:
 the SAME cluster (N=65,536 by default) is column-sharded over the N GPUs
@@ -40,6 +60,7 @@ The JSON line also carries
             configuration, encoding and warm-up (profiles/, FETCH_SIZE x2 +
             WRITE_SIZE, the guide's gfx950 correction; Infinity-Cache hits
             included), null if none was captured at this warm-up.
+and, with --full,
   cpu_baseline: the CPU restatement (oracle/tablesim.c, "port") timed on this
             host's cores (nproc threads and 1 thread) on the full benched
             configuration, plus N=4,096 and N=10 rates and the literal list
@@ -50,7 +71,10 @@ The JSON line also carries
             (N=4,096, k=3, 1% crash at r=8, 64 rounds: the launch-gap regime),
             and the benched configuration with a 1% crash (655 Philox-drawn
             members at r=8, through detection, REMOVE and the tombstones'
-            release: rounds/s and the round count of each kernel variant).
+            release: rounds/s and the round count of each kernel variant);
+            at N>1 the multi-GPU legs (the other shard layout, config 4).
+  placement: the placement, repair and election figures on the benched
+            cluster after its timed rounds (N=1 only, --files).
 """
 from __future__ import annotations
 
@@ -86,6 +110,11 @@ def parse():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0003)
     ap.add_argument("--t-fail", type=int, default=16,
                     help="T_fail = T_cleanup in rounds (reference: 5; see module doc)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs after its last step as DIR/<name>.npy (see module doc)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline figure: cpu_baseline, secondary, placement "
+                         "(each still switched off by its own option below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="timed CPU rounds per rate (at least 1 round)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = nproc (OMP_NUM_THREADS, else the CPU count)")
@@ -427,6 +456,34 @@ def election_leg(gs, eng, n, t_fail):
     return out
 
 
+DUMP_TABLE_BYTES = 24_000_000  # per float64 table: hb + ts + the small arrays stay under 64 MB
+
+
+def dump_outputs(eng, n, st, out_dir, rank):
+    """--dump-outputs (module doc): the timed gh_step call's stats and the
+    state it left, gh_export_state of a fixed seeded sample of observer rows
+    over all N columns, as float64 .npy files (int32 values are exact in
+    float64). Every rank makes the same export calls (they are collective on
+    a sharded cluster); rank 0 writes."""
+    import numpy as np
+    k = max(1, min(n, DUMP_TABLE_BYTES // (8 * n)))
+    rows = np.sort(np.random.default_rng(0x5EED0D07).choice(n, size=k, replace=False))
+    hb = np.empty((k, n), np.float64)
+    ts = np.empty((k, n), np.float64)
+    for x, r in enumerate(rows.tolist()):
+        hb[x], ts[x] = (t[0] for t in eng.export_state(r, 1)[:2])
+    alive = eng.alive()
+    if rank != 0:
+        return
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "round_stats.npy", np.array(list(st.values()), np.float64))
+    np.save(out / "rows.npy", rows.astype(np.float64))
+    np.save(out / "hb_rows.npy", hb)
+    np.save(out / "ts_rows.npy", ts)
+    np.save(out / "alive.npy", alive.astype(np.float64))
+
+
 def make_engine(gs, cfg, rank, world, dist):
     """One engine: the whole cluster (world 1) or rank `rank`'s shard of it
     over RCCL, the unique id broadcast from rank 0 over the gloo group."""
@@ -576,8 +633,10 @@ def main():
     plane_fb = eng.plane_info()[2]
     tier_last = eng.tier_info()
     tier_last_var = eng.tier_info(full=True)[3]
+    if args.dump_outputs:
+        dump_outputs(eng, n, st, args.dump_outputs, rank)
     placement = None
-    if world == 1 and args.files > 0:
+    if args.full and world == 1 and args.files > 0:
         progress("placement and election legs")
         placement = placement_leg(gs, eng, n, args.files, args.t_fail)
         placement["election"] = election_leg(gs, eng, n, args.t_fail)
@@ -585,14 +644,14 @@ def main():
     eng.close()
     per_rank = gather_ranks(dist, rank_roofline(rank, b, kern_ms, launches))
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         secondary = secondary_legs(gs) if world == 1 else multi_gpu_legs(gs, args, rank, world, local, dist)
 
     if rank != 0:
         return
     line = build_line(args, world, elapsed, st, b, kern_ms, launches, per_rank, tier4, plane, tile_w, exch, plane_fb,
                       tier_last, tier_last_var, mem, secondary, placement)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(n, k, args.seed, args.cpu_seconds, args.cpu_threads, args.t_fail)
     print(json.dumps(line), flush=True)
 

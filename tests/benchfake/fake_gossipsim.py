@@ -1,7 +1,8 @@
 """A stand-in for the gossipsim package with the Engine surface bench.py
 uses, for the CPU test of bench.py's argument and JSON plumbing at
 --gpus > 1 (tests/test_bench_plumbing.py). It computes nothing: step()
-returns fixed counters and read_timing() a fixed 1.5 ms per launch. It is
+returns fixed counters, read_timing() a fixed 1.5 ms per launch and
+export_state() a pattern that moves with the timed launches. It is
 injected into sys.modules by tests/benchfake/rank.py only; the product
 package never imports it."""
 GH_COMM_RCCL, GH_COMM_LOCAL = 0, 1
@@ -62,6 +63,19 @@ class Engine:
 
     def sync(self):
         pass
+
+    def export_state(self, row0=0, n_rows=None):
+        """Full rows on every rank (the real call gathers the shards): cell
+        (i, j) holds hb = launches so far + (i + j) % 7 and ts = i - j."""
+        import numpy as np
+        n_rows = self.n - row0 if n_rows is None else n_rows
+        i = np.arange(row0, row0 + n_rows, dtype=np.int32)[:, None]
+        j = np.arange(self.n, dtype=np.int32)[None, :]
+        return self.launches + (i + j) % 7, i - j, np.ones(n_rows, np.uint8)
+
+    def alive(self):
+        import numpy as np
+        return np.ones(self.n, np.uint8)
 
     def exchange_info(self):
         return {"ghost_rows": 22000, "bytes_out": 700 << 20, "bytes_in": 720 << 20}

@@ -22,7 +22,7 @@ case "$1" in
     grep -E "PASSED|FAILED|passed|failed" $out/fullsize.log | cut -c1-200; exit $rc ;;
   bench-pmc)
     rm -rf gpurun_out/pmc
-    timeout -k 10 900 python3 bench.py > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 1; }
+    timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; exit 1; }
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- \
       python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --files 0 > $out/prof.log 2>&1 || exit 1
     bash tools/pmc.sh 5 20 ;;

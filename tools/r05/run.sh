@@ -5,7 +5,7 @@
 #   run.sh suite TAG                      the driver's GPU test command (-m gpu), then the smoke
 #   run.sh tests TAG PYTEST_ARGS...       pytest -m gpu on the given tests / -k filters (-v, prints kept)
 #   run.sh fullsize TAG -k EXPR           tests/test_gpu_fullsize.py --fullsize -k EXPR
-#   run.sh bench TAG                      the driver's bench (--gpus 1 --steps 20 --warmup 5)
+#   run.sh bench TAG                      the driver's bench with every leg (--gpus 1 --steps 20 --warmup 5 --full)
 #   run.sh pmc TAG                        tools/pmc.sh 5 20 (PMC passes + kernel stats of the bench)
 #   run.sh ab TAG VAR V1 V2 [PASSES]      bench A/B of the engine env switch VAR at V1 / V2, alternating
 #   run.sh timeline TAG                   one steady round's kernels (tools/r04/round_timeline.py)
@@ -30,7 +30,7 @@ case "$cmd" in
     timeout -k 10 1100 python -u -m pytest tests/test_gpu_fullsize.py --fullsize -x -v -s $T "$@" \
       > $O/${tag}_fullsize.log 2>&1 || exit 1 ;;
   bench)
-    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench.json 2> $O/${tag}_bench.err || exit 1 ;;
+    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err || exit 1 ;;
   pmc)
     bash tools/pmc.sh 5 20 || exit 1
     cp -r gpurun_out/pmc $O/${tag}_pmc ;;

@@ -3,7 +3,7 @@
 # step has its own time limit and the steps stop at the first failure):
 #   run.sh tests TAG T1 [T2 ...]   pytest node ids (tests/...::name), -m gpu, verbose with prints
 #   run.sh suite TAG               the driver's GPU test command (-m gpu) + smoke
-#   run.sh bench TAG [ARGS...]     the driver's bench (python3 bench.py --gpus 1 --steps 20 --warmup 5 ARGS)
+#   run.sh bench TAG [ARGS...]     the driver's bench with every leg (python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ARGS)
 #   run.sh pmc TAG                 tools/pmc.sh 5 20 (PMC passes + kernel stats of the bench)
 #   run.sh ab TAG VAR [ARGS...]    bench A/B of env switch VAR=1 vs VAR=0, three alternating passes
 #   run.sh timeline TAG            one steady round's kernels (rocprofv3 kernel trace)
@@ -28,7 +28,7 @@ case "$cmd" in
     timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/${tag}_smoke.log 2>&1 || exit 1
     tail -2 $O/${tag}_smoke.log ;;
   bench)
-    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err \
+    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err \
       || { tail $O/${tag}_bench.err; exit 1; }
     tail -c 1500 $O/${tag}_bench.json ;;
   pmc)
