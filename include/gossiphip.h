@@ -196,6 +196,28 @@ int gh_read_detectors(void* h, int32_t* rows, int64_t cap, int64_t* n_out);
  * (member-ID order under GH_ORDER_ID). */
 int gh_lsm(void* h, int32_t observer, int32_t* ids, int32_t* hb, int32_t* ts,
            int64_t cap, int64_t* n_out);
+/* Membership census: per member column, how the running rows see it, and the
+ * age distribution of every view, reduced on the device in one read-only pass
+ * over the table (no reference counterpart; the nearest is running `lsm`,
+ * slave/slave.go:558-561, on every VM). Defined on what gh_export_state
+ * would return now (hb, ts, alive; R = gh_get_round; queued events and the D7
+ * shadow entries are not in it): for member c, S_c = the rows i != c with
+ * alive[i] and hb[i][c] >= 0, T_c = those with hb[i][c] == GH_TOMBSTONE, and
+ * age(i, c) = max(0, R + 1 - ts[i][c]) (SPEC §3, at most INT32_MAX). A
+ * member's own entry is in neither, as in the detector (SPEC §2 step 4).
+ *   listed[c] = |S_c|, tombstoned[c] = |T_c|;
+ *   hb_min[c], hb_max[c] = min / max of hb[i][c] over S_c, hb_sum[c] their sum
+ *     (mean lag = hb_max - hb_sum / listed), age_max[c] = max age(i, c) over
+ *     S_c; an empty S_c gives -1, -1, 0, -1;
+ *   age_hist[b], b < GH_CENSUS_BINS = the (i, c), i in S_c, with
+ *     min(age(i, c), GH_CENSUS_BINS - 1) == b: the sum over b > T_fail is the
+ *     number of step-4 candidates of the next round.
+ * Outputs: [N] each by member id, age_hist [GH_CENSUS_BINS]; any may be NULL.
+ * Additive under ABI 7. On a sharded handle the call is collective: every
+ * rank calls it, and every rank gets the global result. */
+#define GH_CENSUS_BINS 32
+int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min,
+              int32_t* hb_max, int64_t* hb_sum, int32_t* age_max, int64_t* age_hist);
 
 /* MergeMemberList (slave/slave.go:414-440) of one received list into the
  * observer's row at the engine's current tick (the last completed round):

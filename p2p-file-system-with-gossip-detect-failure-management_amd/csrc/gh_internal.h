@@ -1067,3 +1067,16 @@ void launch_vote_scan(const GhDev& d, int cur, const int32_t* mview, int32_t* ou
 // rebuild_file_meta at new master M with its list's first nl (<= 5) members L
 void launch_rebuild(const GhDev& d, int32_t R, int32_t M, const int32_t* L, int32_t nl, int32_t m_listed,
                     int32_t now, hipStream_t s);
+// census.hip (gh_census): one read-only pass over buffer cur (for round r)
+// adds this engine's owned, alive rows into per-local-column accumulators
+// (index c < ncol; the diagonal left out) that reduce across shards with SUM
+// and MAX alone. The caller presets them: listed / tomb / sum / hist 0, cmin /
+// hmax / amax -1 (empty).
+struct GhCensus {
+  int32_t *listed, *tomb;   // observers holding the member present / tombstoned
+  int32_t *cmin;            // INT32_MAX - (lowest present heartbeat): the minimum as a MAX
+  int32_t *hmax, *amax;     // highest present heartbeat / age
+  unsigned long long *sum;  // sum of the present heartbeats
+  unsigned long long *hist; // [GH_CENSUS_BINS] present cells by min(age, GH_CENSUS_BINS - 1)
+};
+void launch_census(const GhDev& d, int cur, int32_t r, const GhCensus& o, hipStream_t s);

@@ -137,6 +137,10 @@ struct Engine {
   // |D| of the last round as read at the end of gh_step (one engine; -1
   // unknown): a first round with a REMOVE pending launches IN 6 on a full grid
   int32_t last_nd = -1;
+  // gh_census accumulators: one block per column shard (the allgather's
+  // slices), one in all for a single engine or row shards
+  char* cs_buf = nullptr;
+  size_t cs_bytes = 0;
   std::string err;
   std::vector<void*> allocs;
 };
@@ -2477,6 +2481,73 @@ int gh_vote_scan(void* h, const int32_t* mview, int32_t* first, int32_t* list_le
     if (first) first[i] = host[i] > 0 ? n - host[i] : -1;
     if (has_master) has_master[i] = (uint8_t)host[n + i];
     if (list_len) list_len[i] = host[2 * (size_t)n + i];
+  }
+  return GH_OK;
+}
+
+// SPEC §3 ages and the views of every member column, reduced on the device
+// (census.hip). Accumulator block of one shard, ncs columns: age bins u64
+// [GH_CENSUS_BINS], heartbeat sums u64, listed, tombstoned (SUM), then the
+// complemented minimum, the maximum and the oldest age (MAX, -1 = none).
+// Column shards: the owner of a column holds its whole answer, the blocks
+// are allgathered and the bins summed. Row shards (and one engine): every
+// shard holds partial answers for all columns, summed / maximised in place.
+int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min, int32_t* hb_max, int64_t* hb_sum,
+              int32_t* age_max, int64_t* age_hist) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  const GhDev& d = e->d;
+  const size_t ncs = (size_t)d.ncs;
+  const bool gather = !e->rowlay && e->world > 1;
+  const int nblk = gather ? e->world : 1;
+  const size_t head = sizeof(uint64_t) * (GH_CENSUS_BINS + ncs);  // bins + sums
+  const size_t blk = head + sizeof(int32_t) * 5 * ncs;
+  if (e->cs_bytes < blk * nblk) {
+    char* nb = nullptr;
+    if ((rc = dalloc(e, &nb, blk * nblk, 0))) return rc;
+    dfree(e, e->cs_buf);
+    e->cs_buf = nb;
+    e->cs_bytes = blk * nblk;
+  }
+  char* mine = e->cs_buf + (gather ? blk * e->rank : 0);
+  GhCensus o;
+  o.hist = reinterpret_cast<unsigned long long*>(mine);
+  o.sum = o.hist + GH_CENSUS_BINS;
+  o.listed = reinterpret_cast<int32_t*>(mine + head);
+  o.tomb = o.listed + ncs;
+  o.cmin = o.tomb + ncs;
+  o.hmax = o.cmin + ncs;
+  o.amax = o.hmax + ncs;
+  HIPCHK(e, hipMemsetAsync(mine, 0, head + sizeof(int32_t) * 2 * ncs, e->stream));
+  HIPCHK(e, hipMemsetAsync(o.cmin, 0xFF, sizeof(int32_t) * 3 * ncs, e->stream));
+  launch_census(d, e->cur, e->round + 1, o, e->stream);  // (the current buffer is for the round about to run)
+  HIPCHK(e, hipGetLastError());
+  if (gather) {
+    COMMCHK(e, e->comm->allgather(mine, e->cs_buf, blk, e->stream));
+    COMMCHK(e, e->comm->allreduce(o.hist, o.hist, GH_CENSUS_BINS, GH_DT_U64, GH_OP_SUM, e->stream));
+  } else {
+    COMMCHK(e, e->comm->allreduce(o.hist, o.hist, GH_CENSUS_BINS + ncs, GH_DT_U64, GH_OP_SUM, e->stream));
+    COMMCHK(e, e->comm->allreduce(o.listed, o.listed, 2 * ncs, GH_DT_I32, GH_OP_SUM, e->stream));
+    COMMCHK(e, e->comm->allreduce(o.cmin, o.cmin, 3 * ncs, GH_DT_I32, GH_OP_MAX, e->stream));
+  }
+  std::vector<char> host(blk * nblk);
+  HIPCHK(e, hipMemcpyAsync(host.data(), e->cs_buf, host.size(), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (age_hist) std::memcpy(age_hist, host.data() + (gather ? blk * e->rank : 0), sizeof(int64_t) * GH_CENSUS_BINS);
+  for (int g = 0; g < nblk; ++g) {
+    const char* b = host.data() + blk * g;
+    const int64_t c0 = gather ? (int64_t)g * d.ncs : 0;
+    const int64_t nc = std::max<int64_t>(0, std::min<int64_t>(d.ncs, e->n - c0));
+    const int32_t* w = reinterpret_cast<const int32_t*>(b + head);
+    if (hb_sum && nc > 0) std::memcpy(hb_sum + c0, b + sizeof(uint64_t) * GH_CENSUS_BINS, sizeof(int64_t) * nc);
+    if (listed && nc > 0) std::memcpy(listed + c0, w, sizeof(int32_t) * nc);
+    if (tombstoned && nc > 0) std::memcpy(tombstoned + c0, w + ncs, sizeof(int32_t) * nc);
+    if (hb_max && nc > 0) std::memcpy(hb_max + c0, w + 3 * ncs, sizeof(int32_t) * nc);
+    if (age_max && nc > 0) std::memcpy(age_max + c0, w + 4 * ncs, sizeof(int32_t) * nc);
+    for (int64_t c = 0; hb_min && c < nc; ++c) hb_min[c0 + c] = w[2 * ncs + c] < 0 ? -1 : INT32_MAX - w[2 * ncs + c];
   }
   return GH_OK;
 }

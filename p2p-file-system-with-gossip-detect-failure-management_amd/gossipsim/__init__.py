@@ -31,7 +31,10 @@ from ._abi import (GH_COMM_LOCAL, GH_COMM_RCCL, GH_DETECT_CANONICAL, GH_DETECT_Q
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
                    GH_PEER_RING, Config, PlanEntry)
 
-__all__ = ["Engine", "ShardGroup", "Cluster", "GossipError", "default_config", "comm_unique_id", "Config"]
+__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "GossipError", "default_config", "comm_unique_id", "Config"]
+
+# gh_census: per member id [N] (age_hist: [GH_CENSUS_BINS] over every listed cell)
+Census = namedtuple("Census", "listed tombstoned hb_min hb_max hb_sum age_max age_hist")
 
 
 class GossipError(RuntimeError):
@@ -303,6 +306,19 @@ class Engine:
         k = n.value
         return ids[:k], hb[:k], ts[:k]
 
+    def census(self):
+        """Membership census of the current table, reduced on the device
+        (gh_census): per member, over the running rows other than its own,
+        how many list it / hold it tombstoned, min / max / sum of the listed
+        heartbeats (-1, -1, 0 when nobody lists it), the oldest listed age
+        (-1), and age_hist[b] = listed cells of age b (the last bin: that or
+        older). Defined on what export_state would return now."""
+        n = self.n
+        out = Census(np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32),
+                     np.empty(n, np.int64), np.empty(n, np.int32), np.empty(_abi.GH_CENSUS_BINS, np.int64))
+        self._chk(self.lib.gh_census(self.h, *[_p(a) for a in out]))
+        return out
+
     def merge_list(self, observer, ids, hb):
         """MergeMemberList (slave/slave.go:414-440) of a received list into
         `observer`'s row now; returns the number of cells changed."""
@@ -555,6 +571,11 @@ class Cluster:
     def lsm(self, member):
         ids, hb, ts = self.engine.lsm(member)
         return list(zip(ids.tolist(), hb.tolist(), ts.tolist()))
+
+    def census(self):
+        """Every member's view count, heartbeat spread and age distribution
+        over the running members (Engine.census)."""
+        return self.engine.census()
 
     # wire format of the gossip datagrams (slave/slave.go:365-385, 527-542)
     def datagram(self, member) -> bytes:

@@ -32,6 +32,7 @@ GH_COMM_ID_BYTES = 128
 GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS = 0, 1
 GH_ORDER_ID, GH_ORDER_APPEND = 0, 1
 GH_REMOVE_ALL, GH_REMOVE_LIST = 0, 1
+GH_CENSUS_BINS = 32
 
 
 class Config(C.Structure):
@@ -82,6 +83,7 @@ SYMBOLS = [
     ("gh_read_failed", C.c_int, [_vp, _vp, _i64]),
     ("gh_read_detectors", C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     ("gh_lsm", C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _P(_i64)]),
+    ("gh_census", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gh_merge_list", C.c_int, [_vp, _i32, _vp, _vp, _i64, _P(_i64)]),
     ("gh_put", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     ("gh_put_conflicts", C.c_int, [_vp, _vp, _i64, _i32, _vp]),
