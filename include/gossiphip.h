@@ -377,6 +377,31 @@ int gh_memory_info(void* h, int64_t* device_bytes, int64_t* wide_used, int64_t* 
  * timestamps; *shards = G (1 for one engine); *held = the files put and not
  * deleted in this shard's slots. Any output may be NULL. Diagnostic. */
 int gh_file_info(void* h, int64_t* slots, int32_t* shards, int64_t* held);
+/* The A/B and diagnostic switches this engine runs with (diagnostic; read-only).
+ * gh_create reads each from the environment variable GH_<name> once, so an
+ * engine keeps the values of its creation and the next engine of the process
+ * may get others; results never depend on them (DESIGN.md measures against
+ * each). out[GH_KNOB_x] = the value in effect: QUIRK_ROWS 1 the one-pass
+ * quirk pre-pass where it applies (0 the two-sweep one); JOBS_FLAT 1 lane
+ * jobs dealt one per lane (0 by region); RMV_FULL7 1 the full-grid REMOVE
+ * launch without a block loop; DNW / NREC 1 the nibble path's move words /
+ * row records are kept (0 also where they do not apply: shards); SIDE 0 / 1 /
+ * 2 side streams of the idle round variants, SIDE_ORDER their order,
+ * JOIN_STAMP how they join; FORCE_SLOW / FORCE_STORM every segment by the
+ * per-cell rule / the storm variant every round; ROUND_NT, ROUND_TPW,
+ * ROUND_XMAP k_round's non-temporal streams, tiles per workgroup and tile
+ * map; SLOW_GRID workgroups of the per-cell kernel; NIB_RMV, NIB_DMA REMOVE
+ * on / LDS-DMA staging of the nibble path; GX_DIRECT same-device row shards
+ * gather their ghosts' planes in place; TMODE the timing mode; PLANE, C8 the
+ * sender plane and the 4-bit tier are kept. Writes min(n_out, GH_KNOB_COUNT)
+ * values; *count (may be NULL) = GH_KNOB_COUNT. No reference counterpart. */
+enum {
+  GH_KNOB_QUIRK_ROWS = 0, GH_KNOB_JOBS_FLAT, GH_KNOB_RMV_FULL7, GH_KNOB_DNW, GH_KNOB_NREC, GH_KNOB_SIDE,
+  GH_KNOB_SIDE_ORDER, GH_KNOB_JOIN_STAMP, GH_KNOB_FORCE_SLOW, GH_KNOB_FORCE_STORM, GH_KNOB_ROUND_NT,
+  GH_KNOB_ROUND_TPW, GH_KNOB_SLOW_GRID, GH_KNOB_NIB_RMV, GH_KNOB_NIB_DMA, GH_KNOB_GX_DIRECT,
+  GH_KNOB_ROUND_XMAP, GH_KNOB_TMODE, GH_KNOB_PLANE, GH_KNOB_C8, GH_KNOB_COUNT
+};
+int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count);
 /* The HBM one shard (rank of world, layout and sizes from cfg) would hold,
  * without a device or a communicator (a dry walk of gh_create's
  * allocations): *create_bytes = everything gh_create allocates;

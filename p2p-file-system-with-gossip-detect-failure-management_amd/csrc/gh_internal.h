@@ -292,6 +292,8 @@ struct GhDev {
   uint32_t *a4[2];  // 4-bit tier: age plane per buffer (null: tier off); with pl[b] it holds buffer b
   int32_t *m8;      // [0..1] buffer b is in the 4-bit tier; [2] this round switches the next buffer's tier;
                     // [3] escaped chunks the round wrote; [4] the round variant that ran (gh_tier_info)
+                    // [5] row layout: a lane job needs its ghost senders' codes (ghost_codes_if_slow);
+                    // [6] launch_round's variant number of the k_round that ran (4: the REMOVE-taking nibble path)
   uint32_t *pl[2];  // sender snapshot plane per buffer (null: plane off)
   int32_t *pvalid;  // [2]: plane of buffer b written by the round that wrote b
   int32_t *pfb;     // waves of the last round that gathered 16-bit codes with a valid plane
@@ -899,6 +901,9 @@ struct GhRound {
   int32_t shadow_row;   // the introducer while it may hold D7 shadow entries (its segments take k_round_slow), else -1
   int32_t vslot;        // the round's index in its gh_step call (vlog: which k_round variant ran)
   int32_t rmv_full;     // k_round IN 6 on a full grid: the host knows a REMOVE is pending this round
+  int32_t rmv_full7;    // ... launched as IN 7, without the block loop (GH_RMV_FULL7=0: IN 6, A/B)
+  int32_t jobs_flat;    // the lane jobs dealt one per lane, k_round_jobs_flat (GH_JOBS_FLAT=0: one region at a time, A/B)
+  int32_t slow_grid;    // workgroups of k_round_slow (GH_SLOW_GRID, A/B)
   int32_t plane;        // the round writes the next buffer's sender plane (and may read cur's)
   int32_t ring_whole;   // ring mode: one engine and a current flag count, so the targets may come
                         // from whole lists when no REMOVE / flag is pending (k_ring_fast)

@@ -132,6 +132,12 @@ struct Engine {
   int gx_direct = 1;  // GH_GX_DIRECT=0: same-device in-process row shards pack and copy their ghosts' planes (A/B)
   GxPeers gx_pub{};   // what this shard publishes for the direct gather (entry 0)
   int side_order = 0;  // GH_SIDE_ORDER=1: the side stream's idle variants as IN 1, IN 3, storm, IN 6 (A/B)
+  // read by gh_create like the switches above, so that an engine created
+  // after the variable changed gets the new value (gh_debug_knobs reports them)
+  int jobs_flat = 1;   // GH_JOBS_FLAT=0: the region-form k_round_jobs (A/B)
+  int rmv_full7 = GH_RMV_FULL7;  // GH_RMV_FULL7=0: the full-grid REMOVE launch as IN 6 (A/B)
+  int slow_grid = 768;  // GH_SLOW_GRID: workgroups of k_round_slow (A/B)
+  int dnw = 1, nrec = 1;  // GH_DNW=0 / GH_NREC=0 (A/B; the buffers are allocated only where they apply)
   int32_t* vlog = nullptr;
   int64_t vlog_cap = 0;
   // |D| of the last round as read at the end of gh_step (one engine; -1
@@ -221,6 +227,9 @@ GhRound round_params(const Engine* e, int32_t r) {
   p.force_slow = e->force_slow;
   p.nib_rmv = e->nib_rmv;
   p.nib_dma = e->nib_dma;
+  p.rmv_full7 = e->rmv_full7;
+  p.jobs_flat = e->jobs_flat;
+  p.slow_grid = e->slow_grid;
   p.shadow_row = e->shadow_any ? e->cfg.introducer : -1;
   p.plane = e->plane;
   // (a row shard holds its senders' whole rows: their lists)
@@ -1129,6 +1138,11 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   if (const char* v = std::getenv("GH_QUIRK_ROWS")) e->quirk_rows = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_GX_DIRECT")) e->gx_direct = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_C8")) e->c8 = e->c8 && std::atoi(v) != 0;
+  if (const char* v = std::getenv("GH_JOBS_FLAT")) e->jobs_flat = std::atoi(v) != 0;
+  if (const char* v = std::getenv("GH_RMV_FULL7")) e->rmv_full7 = GH_RMV_FULL7 && std::atoi(v) != 0;
+  if (const char* v = std::getenv("GH_SLOW_GRID")) e->slow_grid = std::min(65536, std::max(1, std::atoi(v)));
+  if (const char* v = std::getenv("GH_DNW")) e->dnw = std::atoi(v) != 0;  // 0: the nibble path derives the moves from the bases (A/B)
+  if (const char* v = std::getenv("GH_NREC")) e->nrec = std::atoi(v) != 0;  // 0: stage the rows from the inboxes (A/B)
   if (cfg->shard_layout != GH_LAYOUT_COLUMNS && cfg->shard_layout != GH_LAYOUT_ROWS) {
     delete e;
     return GH_EINVAL;
@@ -1236,12 +1250,10 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
         (rc = dalloc(e, &d.stab[0], e->n, 0)) || (rc = dalloc(e, &d.stab[1], e->n, 0)) ||
         (rc = dalloc(e, &d.nquiet, 1, 0)) || (rc = dalloc(e, &d.aq, 1, 0x01)))
       break;
-    const char* dnw_env = std::getenv("GH_DNW");  // 0: the nibble path derives the moves from the bases (A/B)
-    if (e->c8 && !rowlay && !(dnw_env && std::atoi(dnw_env) == 0) &&
+    if (e->c8 && !rowlay && e->dnw &&
         ((rc = dalloc(e, &d.dnw, e->ld / 8, 0)) || (rc = dalloc(e, &d.dbad, e->ld / 8, 0))))
       break;
-    const char* nrec_env = std::getenv("GH_NREC");  // 0: stage the rows from the inboxes (A/B)
-    if (e->c8 && world == 1 && !rowlay && cfg->peer_mode == GH_PEER_PULL && !(nrec_env && std::atoi(nrec_env) == 0) &&
+    if (e->c8 && world == 1 && !rowlay && cfg->peer_mode == GH_PEER_PULL && e->nrec &&
         ((rc = dalloc(e, &d.nmeta, e->n, 0)) || (rc = dalloc(e, &d.nsnd, 4 * (size_t)e->n, 0))))
       break;
     if (e->plane && ((rc = dalloc(e, &d.pl[0], cells / 8, 0xFF)) || (rc = dalloc(e, &d.pl[1], cells / 8, 0xFF))))
@@ -1966,7 +1978,8 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     GhRound pr = p;
     pr.gpo = e->gpo;  // row layout: the ghosts carry only their plane so far
     pr.vslot = q;
-    pr.rmv_full = q == 0 && e->world == 1 && last_nd > 0;
+    // (GH_NIB_RMV=0, the other leg of that A/B: no REMOVE on the nibble path, so no IN 6 / IN 7)
+    pr.rmv_full = q == 0 && e->world == 1 && last_nd > 0 && e->nib_rmv >= 1;
     // the variants of k_round; the ones not selected return at once. With
     // timing on, a launch stamps its own start and end (events 12q + 2v,
     // 12q + 2v + 1 of variant v; hipExtLaunchKernel, no event packets between
@@ -2798,6 +2811,47 @@ int gh_debug_tier(void* h, int32_t row, int64_t c0, int64_t n, uint8_t* out) {
     const int sh = gh_nib((int)(c & 7));
     out[c - c0] = (uint8_t)((((u4 >> sh) & 15u) << 4) | ((a4 >> sh) & 15u));
   }
+  return GH_OK;
+}
+
+// Debug (tests only, not in the header): launch_round's variant number of the
+// k_round that ran in the last round (0 / 2 lean, 1 storm, 3 the nibble path,
+// 4 its REMOVE-taking form, which gh_tier_info reports as 3 too).
+int gh_debug_variant(void* h, int32_t* variant) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e || !variant) return GH_EINVAL;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipMemcpyAsync(variant, e->d.m8 + 6, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e || (!out && n_out > 0) || n_out < 0) return GH_EINVAL;
+  int32_t v[GH_KNOB_COUNT];
+  v[GH_KNOB_QUIRK_ROWS] = e->quirk_rows;
+  v[GH_KNOB_JOBS_FLAT] = e->jobs_flat;
+  v[GH_KNOB_RMV_FULL7] = e->rmv_full7;
+  v[GH_KNOB_DNW] = e->d.dnw != nullptr;  // (in effect: the buffers exist only where the switch applies)
+  v[GH_KNOB_NREC] = e->d.nmeta != nullptr;
+  v[GH_KNOB_SIDE] = e->side;
+  v[GH_KNOB_SIDE_ORDER] = e->side_order;
+  v[GH_KNOB_JOIN_STAMP] = e->join_stamp;
+  v[GH_KNOB_FORCE_SLOW] = e->force_slow;
+  v[GH_KNOB_FORCE_STORM] = e->force_storm;
+  v[GH_KNOB_ROUND_NT] = e->nt;
+  v[GH_KNOB_ROUND_TPW] = e->tpw;
+  v[GH_KNOB_SLOW_GRID] = e->slow_grid;
+  v[GH_KNOB_NIB_RMV] = e->nib_rmv;
+  v[GH_KNOB_NIB_DMA] = e->nib_dma;
+  v[GH_KNOB_GX_DIRECT] = e->gx_direct;
+  v[GH_KNOB_ROUND_XMAP] = e->xmap;
+  v[GH_KNOB_TMODE] = e->tmode;
+  v[GH_KNOB_PLANE] = e->plane;
+  v[GH_KNOB_C8] = e->c8;
+  for (int64_t i = 0; i < std::min<int64_t>(n_out, GH_KNOB_COUNT); ++i) out[i] = v[i];
+  if (count) *count = GH_KNOB_COUNT;
   return GH_OK;
 }
 

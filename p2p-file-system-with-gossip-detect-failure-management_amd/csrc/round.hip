@@ -2171,7 +2171,9 @@ __global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM 
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     d.m8[4] = STORM ? 1 : (IN == 2 || IN == 4 || IN == 5 || IN == 6 || IN == 7) ? 3 : IN == 1 ? 2 : 0;
     // launch_round's variant number of this launch (IN 3 is variant 0 of a tiered engine)
-    if (d.vlog) d.vlog[p.vslot] = STORM ? 1 : (IN == 6 || IN == 7) ? 4 : (IN == 2 || IN == 4 || IN == 5) ? 3 : IN == 1 ? 2 : 0;
+    constexpr int LV = STORM ? 1 : (IN == 6 || IN == 7) ? 4 : (IN == 2 || IN == 4 || IN == 5) ? 3 : IN == 1 ? 2 : 0;
+    d.m8[6] = LV;  // (gh_debug_variant)
+    if (d.vlog) d.vlog[p.vslot] = LV;
   }
   // every running row a quiet candidate and no base moved (one engine): the
   // round reads and writes nothing (a collapsed cluster)
@@ -2554,6 +2556,10 @@ __device__ __forceinline__ bool job_chunk(const GhDev& d, int cur, int dcur, con
       for (int q = 0; q < cnt; ++q) {
         const int s = d.inbox[beg + q];
         if (rmj && gh_rm_at(d, dcur, l0 + j, s)) continue;  // s REMOVEs it before sending
+        if (rmj && d.soleval && !d.rlist) {  // s is its sole detector (row shards: maybe a ghost whose
+          m = max(m, d.soleval[l0 + j]);     // codes did not travel this round, k_round s_need)
+          continue;
+        }
         // the sender's cell from its narrow code (a tier nibble or an escaped
         // code); a wide or stopped sender segment: the redo pass (redo_all)
         const int64_t sl = gh_slot(d, s);
@@ -3555,15 +3561,6 @@ void launch_inbox(const GhDev& d, const GhRound& p, hipStream_t s) {
   hipLaunchKernelGGL(k_inbox_fill, dim3((p.n + 255) / 256), dim3(256), 0, s, d, p);
 }
 
-// the full-grid REMOVE launch as IN 7 (GH_RMV_FULL7=0 at run time: IN 6, A/B)
-static bool rmv_full7() {
-  static const bool on = [] {
-    const char* v = std::getenv("GH_RMV_FULL7");
-    return GH_RMV_FULL7 && (!v || std::atoi(v) != 0);
-  }();
-  return on;
-}
-
 // variant: 0 lean on a 16-bit input, 1 storm, 2 lean on a 4-bit-tier input
 // by the 16-bit rule, 3 the nibble path (IN 2, or IN 4 on row shards), 4 the
 // nibble path that takes REMOVE deliveries (IN 6, column layout)
@@ -3608,7 +3605,7 @@ static bool launch_round_tpw(const GhDev& d, int cur, int dcur, const GhRound& p
           return true;
         case 4:  // the nibble path that takes REMOVE deliveries (column layout; returns at once otherwise)
           if (d.rowlay) return false;
-          if (p.rmv_full && rmv_full7())
+          if (p.rmv_full && p.rmv_full7)  // (GH_RMV_FULL7=0 at run time: IN 6, A/B)
             GH_ROUND_NT(false, 7);
           else
             GH_ROUND_NT(false, 6);
@@ -3633,11 +3630,7 @@ static void round_slow(const GhDev& d, int cur, int dcur, const GhRound& p, hipS
   // one resident generation (150 VGPRs: 3 waves per SIMD, 768 workgroups
   // on 256 CUs); the segments are dealt out by a grid-stride loop, and an
   // idle launch (most rounds) dispatches less (GH_SLOW_GRID: A/B)
-  static const unsigned g = [] {
-    const char* v = std::getenv("GH_SLOW_GRID");
-    return v ? (unsigned)std::max(1, std::atoi(v)) : 768u;
-  }();
-  hipLaunchKernelGGL((k_round_slow<TW>), dim3(g), dim3(256), 0, s, d, cur, dcur, p);
+  hipLaunchKernelGGL((k_round_slow<TW>), dim3((unsigned)p.slow_grid), dim3(256), 0, s, d, cur, dcur, p);
 }
 
 
@@ -3683,18 +3676,11 @@ void launch_finish(const GhDev& d, int dcur, const GhRound& p, hipStream_t s) {
 
 // the lane jobs dealt one per lane (GH_JOBS_FLAT=0 at run time: one region
 // at a time, A/B)
-static bool jobs_flat() {
-  static const bool on = [] {
-    const char* v = std::getenv("GH_JOBS_FLAT");
-    return !v || std::atoi(v) != 0;
-  }();
-  return on;
-}
 template <int TW>
 static void round_jobs(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s) {
   if constexpr (TW >= 64) {
     const unsigned g = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, d.jobw));
-    if (jobs_flat())
+    if (p.jobs_flat)
       hipLaunchKernelGGL((k_round_jobs_flat<TW, GH_JOB_CPL>), dim3(std::min<unsigned>(g, 1024)), dim3(256), 0, s, d,
                          cur, dcur, p);
     else

@@ -146,6 +146,29 @@ class Engine:
         self._chk(self.lib.gh_job_info(self.h, C.byref(nj), C.byref(nr)))
         return nj.value, nr.value
 
+    def knobs(self):
+        """dict GH_<NAME> -> value in effect of every A/B and diagnostic
+        switch gh_create read from the environment for this engine
+        (gh_debug_knobs, read-only): what a test asserts before it trusts
+        that the path it set was the one that ran."""
+        out = (C.c_int32 * len(_abi.KNOBS))()
+        cnt = C.c_int64()
+        self._chk(self.lib.gh_debug_knobs(self.h, out, len(out), C.byref(cnt)))
+        if cnt.value != len(_abi.KNOBS):
+            raise GossipError(_abi.GH_EINVAL, f"gh_debug_knobs reports {cnt.value} switches, the binding {len(out)}")
+        return {"GH_" + k: int(v) for k, v in zip(_abi.KNOBS, out)}
+
+    def debug_variant(self):
+        """launch_round's variant number of the k_round that ran last round:
+        as tier_info(full=True)[3], but 4 for the REMOVE-taking nibble path
+        (gh_debug_variant, test-only and not in the header)."""
+        fn = self.lib.gh_debug_variant
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        fn.restype = C.c_int
+        v = C.c_int32()
+        self._chk(fn(self.h, C.byref(v)))
+        return v.value
+
     def debug_counts(self):
         """(rows whose maintained present count differs from a full recount,
         the first such row or -1): the invariant the <4 guard relies on

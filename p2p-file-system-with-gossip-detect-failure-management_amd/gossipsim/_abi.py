@@ -33,6 +33,11 @@ GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS = 0, 1
 GH_ORDER_ID, GH_ORDER_APPEND = 0, 1
 GH_REMOVE_ALL, GH_REMOVE_LIST = 0, 1
 GH_CENSUS_BINS = 32
+# gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
+# environment variable GH_<NAME> that gh_create reads)
+KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
+         "FORCE_STORM", "ROUND_NT", "ROUND_TPW", "SLOW_GRID", "NIB_RMV", "NIB_DMA", "GX_DIRECT", "ROUND_XMAP",
+         "TMODE", "PLANE", "C8")
 
 
 class Config(C.Structure):
@@ -109,6 +114,7 @@ SYMBOLS = [
     ("gh_export_files", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("gh_import_files", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("gh_set_master", C.c_int, [_vp, C.c_int32]),
+    ("gh_debug_knobs", C.c_int, [_vp, _P(_i32), _i64, _P(_i64)]),
     ("gh_footprint", C.c_int, [_P(Config), _i32, _i32, _i32, _P(_i64), _P(_i64)]),
 ]
 

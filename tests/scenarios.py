@@ -76,6 +76,50 @@ def full_state(n, hb0=2, ts0=0):
     return hb, ts, alive
 
 
+def sole_detector_state(n, world, seed, n_cols=32, p=0.16, t_fail=16, r0=20, lead=0):
+    """(hb, ts, alive, det): a state, to import at round r0, in which n_cols
+    crashed members c are each known to themselves, to a fraction p of the
+    rows (holders) and to one live row det[c] = j whose entry alone is old enough to be
+    detected, in round D = r0 + 1 + lead. With T_cleanup <= T_fail j releases
+    c at once (and may merge it back from a holder), so in round D + 1
+    REMOVE(c) reaches everyone but j (SPEC D4: a sole detector does not
+    message itself): j is then the only sender that still carries c, and a
+    row that has c absent and pulls from j must end the round with c present
+    (unknown REMOVE, then the merge). Everything else is healthy (hb 100,
+    ts r0), so nothing but the REMOVE'd lanes needs the per-cell rule in
+    round D + 1. `world` only documents which row shards the caller counts
+    (sole_detector_cfg is the matching configuration)."""
+    rng = np.random.default_rng(seed)
+    hb = np.full((n, n), 100, np.int32)
+    ts = np.full((n, n), r0, np.int32)
+    alive = np.ones(n, np.uint8)
+    crashed = rng.choice(np.arange(1, n), n_cols, replace=False)
+    alive[crashed] = 0
+    live = np.flatnonzero(alive)
+    det = {}
+    for c in crashed:
+        j = int(rng.choice(live))
+        keep = rng.random(n) < p
+        keep[j] = keep[c] = True  # (c's own, stopped row lists itself: its heartbeat is the column's base)
+        hb[~keep, c] = -1
+        ts[~keep, c] = 0
+        ts[j, c] = r0 - t_fail + lead
+        det[int(c)] = j
+    return hb, ts, alive, det
+
+
+def sole_detector_cfg(seed, t_fail=16):
+    """Pull mode, canonical detection, T_cleanup = T_fail."""
+    return dict(fanout=4, t_fail=t_fail, t_cleanup=t_fail, seed=0x5EED0E00 + seed)
+
+
+# (world, rng seed, lead, p) of the sole-detector runs at N = SOLE_N, imported
+# at round SOLE_R0: test_sole_detector_scenario.py asserts their preconditions
+# on the oracle, test_gpu_rows.py runs them on row shards
+SOLE_N, SOLE_R0 = 2048, 20
+SOLE_CASES = [(2, 1, 0, 0.16), (3, 2, 0, 0.16)]
+
+
 def masked(hb, ts):
     """ts of absent cells carries no meaning in the list model (listsim keeps
     no Member for them); compare it only where hb != -1."""

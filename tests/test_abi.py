@@ -54,6 +54,21 @@ def test_abi_version_and_defaults(abi):
     assert cfg.remove_mode == abi.GH_REMOVE_ALL
 
 
+def test_knob_names_match_header(abi):
+    """gh_debug_knobs fills out[GH_KNOB_x] in the header's enum order; the
+    binding's names (Engine.knobs()) are that enum, in that order, and the
+    call refuses a null handle before touching a device."""
+    enum = re.search(r"enum\s*\{([^}]*GH_KNOB_COUNT[^}]*)\}", HEADER).group(1)
+    names = [x.split("=")[0].strip() for x in enum.split(",") if x.strip()]
+    assert names[-1] == "GH_KNOB_COUNT"
+    assert tuple(n[len("GH_KNOB_"):] for n in names[:-1]) == abi.KNOBS
+    for switch in ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP",
+                   "FORCE_SLOW", "FORCE_STORM", "ROUND_NT", "ROUND_TPW", "SLOW_GRID"):
+        assert switch in abi.KNOBS
+    out = (C.c_int32 * len(abi.KNOBS))()
+    assert abi.load().gh_debug_knobs(None, out, len(out), None) == abi.GH_EINVAL
+
+
 def test_remove_list_validation(abi):
     """GH_REMOVE_LIST is a one-engine, ID-order mode: gh_create and
     gh_footprint refuse it sharded, in append order, or an unknown mode,

@@ -263,3 +263,83 @@ def test_tier_rows(gs, oracle_mod, monkeypatch, world, peer_mode):
     else:  # ring mode has no sender plane: the tier is off, the ghosts carry 16-bit codes
         run_group(gs, oracle_mod, world, rows_cfg(peer_mode=1, seed=0x5EED0890, t_fail=8, t_cleanup=8), n, 16,
                   sched, init=sc.full_state(n))
+
+
+def sole_run(gs, oracle_mod, make, world, seed, lead, p, at_remove=None):
+    """The sole-detector REMOVE scenario (scenarios.py sole_detector_state,
+    preconditions in test_sole_detector_scenario.py) on make(cfg_kw) against
+    the oracle: stats every round, the full tables, failed sets and detectors
+    after rounds D, D + 1 and D + 2; at_remove(eng) after round D + 1."""
+    from test_gpu_sharded import compare
+    n, r0 = sc.SOLE_N, sc.SOLE_R0
+    hb, ts, alive, _ = sc.sole_detector_state(n, world, seed, p=p, r0=r0, lead=lead)
+    cfg = sc.sole_detector_cfg(seed)
+    eng = make(cfg)
+    orc = oracle_mod.Oracle(oracle_mod.default_config(n, **cfg), threads=8)
+    try:
+        eng.import_state(hb, ts, alive, r0)
+        orc.import_state(hb, ts, alive, r0)
+        d_round = r0 + 1 + lead
+        for r in range(r0 + 1, d_round + 3):
+            s1, s2 = eng.step(1), orc.step(1)
+            assert s1 == s2, f"round {r} (D = {d_round}): gpu {s1} != cpu {s2}"
+            if r >= d_round:
+                compare(eng, orc, r)
+            if r == d_round + 1 and at_remove:
+                at_remove(eng)
+    finally:
+        eng.close()
+        orc.close()
+
+
+@pytest.mark.parametrize("jobs_flat", [1, 0], ids=["flat", "region"])
+@pytest.mark.parametrize("direct", [1, 0], ids=["direct", "packed"])
+@pytest.mark.parametrize("world,seed,lead,p", sc.SOLE_CASES)
+def test_sole_detector_remove_rows(gs, oracle_mod, monkeypatch, world, seed, lead, p, direct, jobs_flat):
+    """A REMOVE whose only carrier is a sole detector on another row shard,
+    in a round that is otherwise healthy: the ghosts move as sender planes
+    only (their 16-bit codes stay behind), every shard runs the nibble path,
+    and the rows that have the member absent and pull from the detector take
+    its heartbeat from soleval (round.hip job_chunk, job_rule), not from
+    whatever codes the detector's ghost slot held before. With the lane jobs
+    dealt flat and by region, the ghost planes gathered in place and packed."""
+    monkeypatch.setenv("GH_PLANE", "1")
+    monkeypatch.setenv("GH_GX_DIRECT", str(direct))
+    monkeypatch.setenv("GH_JOBS_FLAT", str(jobs_flat))
+    n = sc.SOLE_N
+    ld = n  # padded columns (n is a multiple of 8 * 256)
+
+    def make(cfg):
+        grp = gs.ShardGroup(gs.default_config(n, shard_layout=ROWS, **cfg), world)
+        kn = grp.knobs()
+        assert (kn["GH_JOBS_FLAT"], kn["GH_GX_DIRECT"], kn["GH_FORCE_SLOW"]) == (jobs_flat, direct, 0), kn
+        return grp
+
+    def at_remove(grp):  # the path under test ran, on every shard
+        for g, (kept, _, _, variant) in enumerate(grp.run("tier_info", full=True)):
+            assert kept == 1 and variant == 3, (g, kept, variant)
+        for g, x in enumerate(grp.run("exchange_info")):
+            assert x["ghost_rows"] > 0 and x["bytes_in"] == x["ghost_rows"] * ld // 2, (g, x)
+
+    sole_run(gs, oracle_mod, make, world, seed, lead, p, at_remove)
+
+
+@pytest.mark.parametrize("form", ["engine", "cols2", "rows_force_slow"])
+def test_sole_detector_remove_other_forms(gs, oracle_mod, monkeypatch, form):
+    """The same scenario on one engine, on 2 column shards, and on row shards
+    with every segment by the per-cell rule (GH_FORCE_SLOW=1, where the
+    ghosts' codes do travel); the oracle is the only judge."""
+    monkeypatch.setenv("GH_PLANE", "1")
+    world, seed, lead, p = sc.SOLE_CASES[0]
+    n = sc.SOLE_N
+    if form == "rows_force_slow":
+        monkeypatch.setenv("GH_FORCE_SLOW", "1")
+
+    def make(cfg):
+        if form == "engine":
+            return gs.Engine(gs.default_config(n, **cfg))
+        eng = gs.ShardGroup(gs.default_config(n, shard_layout=ROWS if form == "rows_force_slow" else 0, **cfg), world)
+        assert eng.knobs()["GH_FORCE_SLOW"] == (form == "rows_force_slow")
+        return eng
+
+    sole_run(gs, oracle_mod, make, world, seed, lead, p)

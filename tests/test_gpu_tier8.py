@@ -319,13 +319,20 @@ def test_tier_tombstones(gs, oracle_mod, t_cleanup):
         assert tier_tombs == 0
 
 
-def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True):
+def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True, on_create=None, per_round=None):
     """Runs the crash wave; returns per round (stats, tier variant, lane
-    jobs) and, for one engine, the final exported state."""
+    jobs) and, for one engine, the final exported state. on_create(eng)
+    runs before the import, per_round(eng, r) after each round."""
     if world > 1:
         eng = gs.ShardGroup(gs.default_config(n, shard_layout=layout, **cfg), world)
     else:
         eng = gs.Engine(gs.default_config(n, **cfg))
+    if on_create:
+        try:
+            on_create(eng)
+        except BaseException:
+            eng.close()
+            raise
     orc = om.Oracle(om.default_config(n, **cfg), threads=8) if check else None
     hb, ts, alive = sc.full_state(n)
     eng.import_state(hb, ts, alive, 0)
@@ -346,6 +353,8 @@ def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True):
                 compare(eng, orc, r)
             var, jobs = (eng.tier_info(full=True)[3], eng.job_info()[0]) if world == 1 else (None, None)
             trace.append((s1, var, jobs))
+            if per_round:
+                per_round(eng, r)
         final = eng.export_state() if world == 1 else None
     finally:
         eng.close()
@@ -372,15 +381,24 @@ def test_tier_remove_on_nibble_path(gs, oracle_mod, monkeypatch, case):
     sched = {8: [(sc.CRASH, int(c)) for c in crashed]}
     rounds = 34
     world, layout = {"cols2": (2, 0), "rows3": (3, 1)}.get(case, (1, 0))
-    trace, final = remove_run(gs, oracle_mod, n, cfg, sched, rounds, world, layout)
+    launched = {}  # round -> launch_round's variant number of the k_round that ran (4: the REMOVE-taking form)
+    trace, final = remove_run(gs, oracle_mod, n, cfg, sched, rounds, world, layout,
+                              per_round=None if world > 1 else lambda e, r: launched.__setitem__(r, e.debug_variant()))
     tomb_rounds = [r for r, (s, _, _) in enumerate(trace, 1) if s["tombstoned"]]
     assert tomb_rounds, trace
     if world > 1:
         return
     # the REMOVE rounds ran the nibble path, with few lane jobs
     assert all(trace[r - 1][1] == 3 for r in tomb_rounds), [(r, trace[r - 1]) for r in tomb_rounds]
+    assert 4 in {launched[r] for r in tomb_rounds}, launched  # (the diagnostic tells the two nibble forms apart)
     monkeypatch.setenv("GH_NIB_RMV", "0")
-    off, final_off = remove_run(gs, oracle_mod, n, cfg, sched, rounds, check=False)
+    launched_off = {}
+    off, final_off = remove_run(gs, oracle_mod, n, cfg, sched, rounds, check=False,
+                                on_create=lambda e: launched_off.__setitem__(0, e.knobs()["GH_NIB_RMV"]),
+                                per_round=lambda e, r: launched_off.__setitem__(r, e.debug_variant()))
+    # the other leg of the A/B: the REMOVE-taking nibble path is never the one selected
+    assert launched_off.pop(0) == 0
+    assert 4 not in launched_off.values(), launched_off
     for r, (a, b) in enumerate(zip(trace, off), 1):
         assert a[0] == b[0], (r, a[0], b[0])
     for x, y in zip(final, final_off):
