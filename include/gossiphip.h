@@ -255,6 +255,60 @@ int gh_get_files(void* h, const int32_t* files, int64_t n, int32_t* replicas,
 int gh_delete_files(void* h, const int32_t* files, int64_t n,
                     int32_t* old_replicas);
 
+/* File-table audit: the master's replica table summarised against an
+ * availability set, reduced on the device in one read-only pass over the file
+ * slots (no reference counterpart: the reference learns this only by running
+ * Update_metadata, master/master.go:74-127, which mutates the table). Defined
+ * on the current file table and membership table; queued events are not
+ * applied, and the table and the draw counters are unchanged.
+ *   A (availability): observer in [0, N): the present members of that row
+ *     (hb[observer][a] >= 0), exactly the `available` of Update_metadata
+ *     (master/master.go:93-99), the set gh_repair(observer) uses. observer ==
+ *     GH_AVAIL_ALIVE: the members with alive[a] as gh_export_state returns it
+ *     now, the ground truth no member of the reference can see. Any other
+ *     value: GH_EINVAL.
+ *   A file f exists iff its version is >= 0. Its working count w(f) = the
+ *     replica slots q < R with 0 <= rep[f][q] < N and rep[f][q] in A: slots,
+ *     not distinct members, as Update_metadata appends them (:93-99).
+ *   *files = the existing files.
+ *   working_hist[b], b < GH_AUDIT_BINS = the existing files with w(f) == b
+ *     (bins above R are 0). working_hist[0]: no working replica (alive mode:
+ *     the file is lost). The sum over b < R is the number of entries
+ *     gh_repair(observer) would plan (in GH_DETECT_CANONICAL its *n_plan).
+ *   *starved = of the files with w < R, those Init_replica would refuse for
+ *     one of its two preconditions (master/master.go:129-135), with the
+ *     current master's candidate list as gh_put / gh_repair obtain it (list
+ *     order under GH_ORDER_APPEND), M its length: M <= 1 (Intn panics), or
+ *     (M - 1) - in_pool < R - w, in_pool = the working slots naming a
+ *     candidate other than the last (the last is never drawn, :135; the loop
+ *     would not end). The 2^20-draw budget of one placement is not predicted.
+ *   load[m] = the existing files with at least one slot naming m (a member
+ *     named twice by one file counts once): len(store(m)), the `store`
+ *     command (slave/slave.go:605, sdfs_slave/sdfs_slave.go:59-68) read from
+ *     the master's metadata. Independent of A.
+ *   sole[m] = the existing files with w(f) == 1 whose one working slot names
+ *     m: the files that die with m.
+ * working_hist: [GH_AUDIT_BINS]; load, sole: [N] by member id; any output may
+ * be NULL. Additive under ABI 7. On a sharded handle both calls are
+ * collective: every rank calls them with the same arguments (the same outputs
+ * NULL), and every rank gets the global result. GH_EINVAL for an engine
+ * created with max_files = 0. */
+#define GH_AVAIL_ALIVE (-1)   /* availability = the running processes      */
+#define GH_AUDIT_BINS 9       /* working replicas 0..8 (replicas is 1..8)  */
+int gh_file_audit(void* h, int32_t observer, int64_t* files, int64_t* working_hist,
+                  int64_t* starved, int32_t* load, int32_t* sole);
+/* The existing files f, in ascending id, with (member < 0 or some slot of f
+ * names `member`) and w(f) <= max_working under the A of `observer` (as
+ * above); max_working in 0..8, max_working >= R disables the condition.
+ * *n_out = their number, the lowest min(*n_out, cap) ids are written.
+ * (any observer, m, 8) is the `store` command at m (slave/slave.go:605);
+ * (GH_AVAIL_ALIVE, -1, 0) the lost files; (o, -1, R - 1) the files
+ * gh_repair(o) would touch; (GH_AVAIL_ALIVE, m, 1) the files lost if m
+ * died. GH_EINVAL for member >= N, max_working outside 0..8, a bad observer,
+ * or a NULL n_out / NULL files with cap > 0. */
+int gh_file_select(void* h, int32_t observer, int32_t member, int32_t max_working,
+                   int32_t* files, int64_t cap, int64_t* n_out);
+
 /* ---- master re-election (SPEC §9; slave/slave.go:930-1051) ------------- */
 /* The master check at the end of updateMemberList (slave/slave.go:451-457)
  * and revote_master's target (:930-948), for every row of the current table:

@@ -1085,3 +1085,26 @@ struct GhCensus {
   unsigned long long *hist; // [GH_CENSUS_BINS] present cells by min(age, GH_CENSUS_BINS - 1)
 };
 void launch_census(const GhDev& d, int cur, int32_t r, const GhCensus& o, hipStream_t s);
+// files.hip (gh_file_audit / gh_file_select): read-only passes over this
+// shard's file slots. abits / mbits: the availability set and the master's
+// list as flat bitmaps over the member ids ((n + 31) / 32 words), written by
+// launch_fa_bits from rbits rows qo / qm of nr gathered rows (qo < 0: alive[];
+// qm < 0: no master bitmap). The audit adds into cnt / load / sole (preset 0;
+// they reduce across shards with SUM); want_starved reads d.cand / d.ncand.
+#define GH_FA_LDS_MAX 1024  // members at most whose load / sole bins a workgroup keeps in LDS
+struct GhFileAudit {
+  const uint32_t *abits, *mbits;
+  unsigned long long* cnt;  // [GH_AUDIT_BINS] working_hist, then files, starved
+  int32_t *load, *sole;     // [n] each; null = not wanted
+  int32_t want_starved;
+};
+void launch_fa_bits(const GhDev& d, int nr, int qm, int qo, uint32_t* abits, uint32_t* mbits, hipStream_t s);
+// lds_n: the workgroups keep load / sole in LDS when n <= min(lds_n, GH_FA_LDS_MAX)
+void launch_file_audit(const GhDev& d, int32_t R, const GhFileAudit& o, int32_t lds_n, hipStream_t s);
+// the ids of the existing files naming `member` (< 0: any) with at most
+// max_working working slots (< 0: any) -> out (fcap ids at most). wgc null:
+// unordered, their count added to *n_out; wgc = GH_FS_WGS words of scratch:
+// ascending, their count written to *n_out
+#define GH_FS_WGS 1024
+void launch_file_select(const GhDev& d, int32_t R, const uint32_t* abits, int32_t member, int32_t max_working,
+                        int32_t* out, unsigned long long* n_out, uint32_t* wgc, hipStream_t s);

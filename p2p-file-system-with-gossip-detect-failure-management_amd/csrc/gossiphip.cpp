@@ -147,6 +147,12 @@ struct Engine {
   // slices), one in all for a single engine or row shards
   char* cs_buf = nullptr;
   size_t cs_bytes = 0;
+  // gh_file_audit / gh_file_select scratch (counters, load / sole, the two
+  // member bitmaps, the selected ids), grown on demand, never shrunk
+  char* fa_buf = nullptr;
+  size_t fa_bytes = 0;
+  int fa_lds_n = 512;  // GH_FA_LDS_N: members up to which the audit's workgroups keep load / sole in LDS (A/B; 0: never)
+  int fs_ordered = 1;  // GH_FS_ORDERED=0: gh_file_select compacts unordered and sorts on the host (A/B)
   std::string err;
   std::vector<void*> allocs;
 };
@@ -1143,6 +1149,8 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   if (const char* v = std::getenv("GH_SLOW_GRID")) e->slow_grid = std::min(65536, std::max(1, std::atoi(v)));
   if (const char* v = std::getenv("GH_DNW")) e->dnw = std::atoi(v) != 0;  // 0: the nibble path derives the moves from the bases (A/B)
   if (const char* v = std::getenv("GH_NREC")) e->nrec = std::atoi(v) != 0;  // 0: stage the rows from the inboxes (A/B)
+  if (const char* v = std::getenv("GH_FA_LDS_N")) e->fa_lds_n = std::min(GH_FA_LDS_MAX, std::max(0, std::atoi(v)));
+  if (const char* v = std::getenv("GH_FS_ORDERED")) e->fs_ordered = std::atoi(v) != 0;
   if (cfg->shard_layout != GH_LAYOUT_COLUMNS && cfg->shard_layout != GH_LAYOUT_ROWS) {
     delete e;
     return GH_EINVAL;
@@ -2562,6 +2570,168 @@ int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min, in
     if (age_max && nc > 0) std::memcpy(age_max + c0, w + 4 * ncs, sizeof(int32_t) * nc);
     for (int64_t c = 0; hb_min && c < nc; ++c) hb_min[c0 + c] = w[2 * ncs + c] < 0 ? -1 : INT32_MAX - w[2 * ncs + c];
   }
+  return GH_OK;
+}
+
+// gh_file_audit / gh_file_select (files.hip). Scratch layout: 16 u64 (the 11
+// audit counters; [12] the select count), load [n], sole [n] (contiguous: one
+// SUM allreduce, one copy out), the availability and master bitmaps, the
+// ordered selection's per-workgroup counts, then this shard's selected ids
+// [fcap].
+struct FaBuf {
+  unsigned long long* cnt;
+  int32_t *load, *sel;
+  uint32_t *abits, *mbits, *wgc;
+};
+static int fa_reserve(Engine* e, FaBuf* b) {
+  const size_t n = (size_t)e->n, nwb = ((n + 31) / 32 * sizeof(uint32_t) + 15) / 16 * 16;
+  const size_t o_load = 16 * sizeof(uint64_t), o_ab = (o_load + 2 * n * sizeof(int32_t) + 15) / 16 * 16;
+  const size_t o_wgc = o_ab + 2 * nwb, o_sel = o_wgc + sizeof(uint32_t) * GH_FS_WGS;
+  const size_t total = o_sel + sizeof(int32_t) * (size_t)e->d.fcap;
+  if (e->fa_bytes < total) {
+    char* nb = nullptr;
+    int rc;
+    if ((rc = dalloc(e, &nb, total, 0))) return rc;
+    dfree(e, e->fa_buf);
+    e->fa_buf = nb;
+    e->fa_bytes = total;
+  }
+  b->cnt = reinterpret_cast<unsigned long long*>(e->fa_buf);
+  b->load = reinterpret_cast<int32_t*>(e->fa_buf + o_load);
+  b->abits = reinterpret_cast<uint32_t*>(e->fa_buf + o_ab);
+  b->mbits = reinterpret_cast<uint32_t*>(e->fa_buf + o_ab + nwb);
+  b->wgc = reinterpret_cast<uint32_t*>(e->fa_buf + o_wgc);
+  b->sel = reinterpret_cast<int32_t*>(e->fa_buf + o_sel);
+  return GH_OK;
+}
+
+// The availability set of `observer` (GH_AVAIL_ALIVE: alive[]) into b.abits
+// and, with_master, the master's list into b.mbits and its candidates into
+// d.cand / d.ncand as gh_put / gh_repair obtain them.
+static int fa_avail(Engine* e, int32_t observer, bool with_master, const FaBuf& b) {
+  std::vector<int32_t> rows;
+  if (with_master) rows.push_back(e->cfg.master);
+  if (observer >= 0) rows.push_back(observer);
+  const int nr = (int)rows.size();
+  int rc;
+  if (nr > 0) {
+    if ((rc = upload(e, e->rows_buf, rows))) return rc;
+    if ((rc = gather_rows(e, e->rows_buf, nr))) return rc;
+  }
+  if (with_master) {
+    if (e->lorder)
+      launch_list_cand(e->d, e->lcur, e->cfg.master, e->stream);
+    else
+      launch_candidates(e->d, nr, e->stream);
+  }
+  launch_fa_bits(e->d, nr, with_master ? 0 : -1, observer >= 0 ? nr - 1 : -1, b.abits, b.mbits, e->stream);
+  HIPCHK(e, hipGetLastError());
+  return GH_OK;
+}
+
+int gh_file_audit(void* h, int32_t observer, int64_t* files, int64_t* working_hist, int64_t* starved, int32_t* load,
+                  int32_t* sole) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (e->cfg.max_files <= 0) return set_err(e, GH_EINVAL, "engine created with max_files = 0");
+  if (observer != GH_AVAIL_ALIVE && (observer < 0 || observer >= e->n)) return set_err(e, GH_EINVAL, "observer");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  FaBuf b;
+  if ((rc = fa_reserve(e, &b))) return rc;
+  const size_t n = (size_t)e->n, head = 16 * sizeof(uint64_t) + 2 * n * sizeof(int32_t);
+  HIPCHK(e, hipMemsetAsync(e->fa_buf, 0, head, e->stream));
+  if ((rc = fa_avail(e, observer, starved != nullptr, b))) return rc;
+  GhFileAudit o;
+  o.abits = b.abits;
+  o.mbits = b.mbits;
+  o.cnt = b.cnt;
+  o.load = load ? b.load : nullptr;
+  o.sole = sole ? b.load + n : nullptr;
+  o.want_starved = starved != nullptr;
+  launch_file_audit(e->d, e->cfg.replicas, o, e->fa_lds_n, e->stream);
+  HIPCHK(e, hipGetLastError());
+  if (e->world > 1) {  // each shard audited its own files
+    COMMCHK(e, e->comm->allreduce(b.cnt, b.cnt, GH_AUDIT_BINS + 2, GH_DT_U64, GH_OP_SUM, e->stream));
+    if (load || sole) COMMCHK(e, e->comm->allreduce(b.load, b.load, 2 * n, GH_DT_I32, GH_OP_SUM, e->stream));
+  }
+  std::vector<char> host(load || sole ? head : 16 * sizeof(uint64_t));
+  HIPCHK(e, hipMemcpyAsync(host.data(), e->fa_buf, host.size(), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const int64_t* c = reinterpret_cast<const int64_t*>(host.data());
+  if (working_hist) std::memcpy(working_hist, c, sizeof(int64_t) * GH_AUDIT_BINS);
+  if (files) *files = c[GH_AUDIT_BINS];
+  if (starved) *starved = c[GH_AUDIT_BINS + 1];
+  const char* w = host.data() + 16 * sizeof(uint64_t);
+  if (load) std::memcpy(load, w, sizeof(int32_t) * n);
+  if (sole) std::memcpy(sole, w + sizeof(int32_t) * n, sizeof(int32_t) * n);
+  return GH_OK;
+}
+
+int gh_file_select(void* h, int32_t observer, int32_t member, int32_t max_working, int32_t* files, int64_t cap,
+                   int64_t* n_out) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e || !n_out || (cap > 0 && !files)) return GH_EINVAL;
+  if (e->cfg.max_files <= 0) return set_err(e, GH_EINVAL, "engine created with max_files = 0");
+  if (observer != GH_AVAIL_ALIVE && (observer < 0 || observer >= e->n)) return set_err(e, GH_EINVAL, "observer");
+  if (member >= e->n) return set_err(e, GH_EINVAL, "member");
+  if (max_working < 0 || max_working >= GH_AUDIT_BINS) return set_err(e, GH_EINVAL, "max_working");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  FaBuf b;
+  if ((rc = fa_reserve(e, &b))) return rc;
+  const int R = e->cfg.replicas;
+  const bool by_w = max_working < R;  // w <= R always
+  unsigned long long* cnt = b.cnt + 12;
+  HIPCHK(e, hipMemsetAsync(cnt, 0, sizeof(uint64_t), e->stream));
+  if (by_w && (rc = fa_avail(e, observer, false, b))) return rc;
+  launch_file_select(e->d, R, b.abits, member, by_w ? max_working : -1, b.sel, cnt, e->fs_ordered ? b.wgc : nullptr,
+                     e->stream);
+  HIPCHK(e, hipGetLastError());
+  std::vector<int32_t> all;
+  if (e->world > 1) {
+    // each shard selected among its own files: allgather the counts, then
+    // the ids (padded to the largest count), as gh_repair gathers its plan
+    const int G = e->world;
+    Staging sc;
+    if ((rc = sc.alloc(e, sizeof(uint64_t) * (G + 1)))) return rc;
+    uint64_t* dc = sc.as<uint64_t>();
+    HIPCHK(e, hipMemcpyAsync(dc + G, cnt, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
+    COMMCHK(e, e->comm->allgather(dc + G, dc, sizeof(uint64_t), e->stream));
+    std::vector<uint64_t> counts(G);
+    HIPCHK(e, hipMemcpyAsync(counts.data(), dc, sizeof(uint64_t) * G, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const size_t mx = (size_t)*std::max_element(counts.begin(), counts.end());
+    if (mx > 0) {
+      Staging sp;
+      const size_t B = sizeof(int32_t) * mx;
+      if ((rc = sp.alloc(e, B * (G + 1)))) return rc;
+      char* base = sp.as<char>();
+      if (counts[e->rank] > 0)
+        HIPCHK(e, hipMemcpyAsync(base + B * G, b.sel, sizeof(int32_t) * counts[e->rank], hipMemcpyDeviceToDevice,
+                                 e->stream));
+      COMMCHK(e, e->comm->allgather(base + B * G, base, B, e->stream));
+      std::vector<int32_t> got(mx * G);
+      HIPCHK(e, hipMemcpyAsync(got.data(), base, B * G, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      for (int g = 0; g < G; ++g) all.insert(all.end(), got.begin() + (size_t)g * mx, got.begin() + (size_t)g * mx + counts[g]);
+    }
+  } else {
+    uint64_t k = 0;
+    HIPCHK(e, hipMemcpyAsync(&k, cnt, sizeof k, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    all.resize(k);
+    if (k > 0) {
+      HIPCHK(e, hipMemcpyAsync(all.data(), b.sel, sizeof(int32_t) * k, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+  }
+  if (!e->fs_ordered || e->world > 1) std::sort(all.begin(), all.end());  // (each shard's ids ascend: files g, g + G, ...)
+  const int64_t total = (int64_t)all.size();
+  if (std::min(total, cap) > 0) std::memcpy(files, all.data(), sizeof(int32_t) * std::min(total, cap));
+  *n_out = total;
   return GH_OK;
 }
 

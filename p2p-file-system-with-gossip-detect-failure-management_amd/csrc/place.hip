@@ -46,7 +46,8 @@ __device__ int init_replica(const GhDev& d, int32_t nr, int32_t f, int64_t fl, i
   int in_pool = 0;
   for (int x = 0; x < len; ++x) {
     const int32_t a = nodes[x];
-    in_pool += (a >= 0 && a < d.n && a < last && gh_gbit(d, d.rbits, nr, 0, a));
+    // (the last candidate by position: in list order it need not be the highest id)
+    in_pool += (a >= 0 && a < d.n && a != last && gh_gbit(d, d.rbits, nr, 0, a));
   }
   if ((M - 1) - in_pool < R - len) return GH_EPLACEMENT_STARVED;  // infinite loop
   uint32_t dr = d.draws[fl];

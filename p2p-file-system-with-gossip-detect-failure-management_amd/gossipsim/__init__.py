@@ -26,15 +26,19 @@ from concurrent.futures import FIRST_EXCEPTION, ThreadPoolExecutor, wait
 import numpy as np
 
 from . import _abi, codec
-from ._abi import (GH_COMM_LOCAL, GH_COMM_RCCL, GH_DETECT_CANONICAL, GH_DETECT_QUIRK,  # noqa: F401
+from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, GH_DETECT_CANONICAL,  # noqa: F401
+                   GH_DETECT_QUIRK,
                    GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS, GH_ORDER_APPEND, GH_ORDER_ID, GH_REMOVE_ALL, GH_REMOVE_LIST,
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
                    GH_PEER_RING, Config, PlanEntry)
 
-__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "GossipError", "default_config", "comm_unique_id", "Config"]
+__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "GossipError", "default_config",
+           "comm_unique_id", "Config"]
 
 # gh_census: per member id [N] (age_hist: [GH_CENSUS_BINS] over every listed cell)
 Census = namedtuple("Census", "listed tombstoned hb_min hb_max hb_sum age_max age_hist")
+# gh_file_audit: files, starved ints; working_hist int64 [GH_AUDIT_BINS]; load, sole int32 [N] by member id
+FileAudit = namedtuple("FileAudit", "files working_hist starved load sole")
 
 
 class GossipError(RuntimeError):
@@ -395,6 +399,35 @@ class Engine:
         self._chk(self.lib.gh_delete_files(self.h, _p(f), len(f), _p(rep)))
         return rep
 
+    def file_audit(self, observer=GH_AVAIL_ALIVE):
+        """File-table audit against an availability set, reduced on the
+        device (gh_file_audit, read-only): `observer`'s present members (the
+        set repair(observer) would use) or, by default, the running processes.
+        FileAudit(files, working_hist, starved, load, sole): the existing
+        files, those with b working replica slots (working_hist[0]: none left;
+        sum(working_hist[:R]): the entries repair(observer) would plan), those
+        of them placement would refuse, and per member the files it holds
+        (len(store(m))) and the files whose only working replica it is."""
+        files, starved = C.c_int64(), C.c_int64()
+        hist = np.empty(GH_AUDIT_BINS, np.int64)
+        load = np.empty(self.n, np.int32)
+        sole = np.empty(self.n, np.int32)
+        self._chk(self.lib.gh_file_audit(self.h, int(observer), C.byref(files), _p(hist), C.byref(starved),
+                                         _p(load), _p(sole)))
+        return FileAudit(files.value, hist, starved.value, load, sole)
+
+    def file_select(self, observer=GH_AVAIL_ALIVE, member=-1, max_working=8, cap=None):
+        """Ascending ids (int32) of the existing files that name `member`
+        (-1: any) and have at most `max_working` working replica slots under
+        `observer`'s availability (>= R: any); at most `cap` of them, the
+        lowest (gh_file_select)."""
+        cap = int(self.cfg.max_files) if cap is None else int(cap)
+        out = np.empty(max(cap, 1), np.int32)
+        n = C.c_int64()
+        self._chk(self.lib.gh_file_select(self.h, int(observer), int(member), int(max_working), _p(out), cap,
+                                          C.byref(n)))
+        return out[: min(n.value, cap)].copy()
+
     # ---- master re-election (SPEC §9) -------------------------------------
     def vote_scan(self, mview):
         """Per row: MemberList[0] (-1 if empty), len(MemberList), and whether
@@ -714,10 +747,18 @@ class Cluster:
         return self.engine.delete_files(files)
 
     def store(self, member):
-        """Files with a replica on `member` (sdfs_slave Local_files)."""
-        f = np.arange(self.engine.cfg.max_files, dtype=np.int32)
-        rep, ver = self.engine.get_files(f)
-        return f[(ver >= 0) & (rep == member).any(axis=1)].tolist()
+        """Files with a replica on `member` (sdfs_slave Local_files), read
+        from the master's metadata on the device (Engine.file_select)."""
+        if self.engine.cfg.max_files <= 0 or not 0 <= int(member) < self.n:
+            return []
+        return self.engine.file_select(member=int(member)).tolist()
+
+    def audit(self, observer=None):
+        """Durability of the file table (Engine.file_audit) as `observer`
+        sees the cluster, or against the running processes (None). The latter
+        is the engine's alive vector: a member in `dead` whose crash event the
+        next round has yet to apply still counts as running."""
+        return self.engine.file_audit(GH_AVAIL_ALIVE if observer is None else int(observer))
 
     def tick(self, rounds=1):
         """Run rounds one at a time, running due repair passes after each."""

@@ -33,6 +33,8 @@ GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS = 0, 1
 GH_ORDER_ID, GH_ORDER_APPEND = 0, 1
 GH_REMOVE_ALL, GH_REMOVE_LIST = 0, 1
 GH_CENSUS_BINS = 32
+GH_AVAIL_ALIVE = -1
+GH_AUDIT_BINS = 9
 # gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
 # environment variable GH_<NAME> that gh_create reads)
 KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
@@ -95,6 +97,8 @@ SYMBOLS = [
     ("gh_repair", C.c_int, [_vp, _i32, _P(PlanEntry), _i64, _P(_i64)]),
     ("gh_get_files", C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     ("gh_delete_files", C.c_int, [_vp, _vp, _i64, _vp]),
+    ("gh_file_audit", C.c_int, [_vp, _i32, _P(_i64), _vp, _P(_i64), _vp, _vp]),
+    ("gh_file_select", C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _P(_i64)]),
     ("gh_vote_scan", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("gh_rebuild_meta", C.c_int, [_vp, _i32, _P(_i32), _P(_i64)]),
     ("gh_set_round_variant", C.c_int, [_vp, _i32, _i32]),
