@@ -219,6 +219,77 @@ int gh_lsm(void* h, int32_t observer, int32_t* ids, int32_t* hb, int32_t* ts,
 int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min,
               int32_t* hb_max, int64_t* hb_sum, int32_t* age_max, int64_t* age_hist);
 
+/* Detection journal: what a failure detector is judged by -- how long a crash
+ * takes to be detected, how often a running member is declared dead, how long
+ * the verdict takes to reach every view -- kept on the device and updated once
+ * per round inside gh_step by one O(N) kernel, read out on demand (no
+ * reference counterpart: the reference only logs each detection,
+ * detectfailure slave/slave.go:460-482, and each REMOVE it sends, Remove
+ * :338-363). Off by default: gh_step then launches and allocates nothing new,
+ * and gh_create's allocations and gh_footprint do not include it.
+ * gh_journal_enable: mode GH_JOURNAL_OFF / DETECT / VIEWS (any other:
+ * GH_EINVAL), log_rounds in 0..2^20 (else GH_EINVAL) = the rounds the log ring
+ * keeps. Every call clears the journal (re-enabling restarts it); a non-off
+ * mode allocates it and takes the current alive[] as the baseline.
+ * gh_import_state and gh_init_full clear it too and take the new alive[]. It
+ * persists across gh_step calls; a round a call did not run (GH_ERANGE) is
+ * not journaled.
+ *   For a journaled round r, after the round: a[c] = alive[c] as the round ran
+ *   (after its events), pa[c] = a[c] of the previous journaled round or the
+ *   baseline, cnt[c] / dmin[c] = the rows that detected member c in round r
+ *   (the cells detectfailure removed, slave/slave.go:472) and the lowest of
+ *   them, running = sum of a. Per member c, in this order:
+ *   1. a && !pa: start_round = r, stop_round = -1. !a && pa: stop_round = r.
+ *      Either resets the phase: first_round = first_detector = -1,
+ *      first_count = 0, forgotten_round = known_round = -1. Fields never set
+ *      are -1 (a member stopped before the baseline keeps stop_round = -1).
+ *   2. cnt > 0: det_rounds++, detectors += cnt, last_round = r; if a (a false
+ *      positive) fp_rounds++. If first_round < 0: first_round = r,
+ *      first_detector = dmin, first_count = cnt, and if !a && stop_round >= 0
+ *      latency_hist[min(r - stop_round, GH_JOURNAL_BINS - 1)]++: the detection
+ *      latency, once per stop.
+ *   3. GH_JOURNAL_VIEWS only, L = gh_census's listed[c] of the table after
+ *      round r: !a && forgotten_round < 0 && L == 0: forgotten_round = r, and
+ *      if stop_round >= 0 forget_hist[min(r - stop_round, BINS - 1)]++;
+ *      a && known_round < 0 && L == running - 1: known_round = r, and if
+ *      start_round >= 0 known_hist[min(r - start_round, BINS - 1)]++. In
+ *      DETECT mode both fields stay -1 and both histograms 0.
+ *   The round's log entry (gh_journal_round): round = r, running; failed =
+ *   |D_r| (gh_round_stats.failed_members of that round), false_failed = the
+ *   running members among them; detections = sum of cnt (gh_round_stats.
+ *   detections of that round), false_detections = that over the running
+ *   members; stale_views = sum of L over the stopped members, missing_views =
+ *   sum of (running - 1 - L) over the running ones (both -1 without VIEWS).
+ * gh_journal_read: per-member outputs [N] by member id, the histograms
+ * [GH_JOURNAL_BINS]; any output may be NULL. gh_journal_rounds: the log is a
+ * ring of the last log_rounds rounds; *n_total = the rounds journaled since
+ * enable, the newest *n_out = min(*n_total, log_rounds, cap) entries are
+ * written, oldest first (n_total, n_out may be NULL; out may be NULL with
+ * cap 0). With the journal off both return GH_EINVAL; a NULL handle returns
+ * GH_EINVAL from all three before any device is touched. Cost per round, at
+ * N = 65,536, k = 4 on a MI355X (DESIGN.md "Journal"): DETECT one O(N) launch,
+ * 8.5 us beside a 2.14 ms round; VIEWS adds one census pass over the table per
+ * round, 1.60 ms: a round then takes 1.74 times as long.
+ * Additive under ABI 7. On a sharded handle all three calls are collective:
+ * every rank calls them with the same arguments (the same outputs NULL), and
+ * every rank gets the global result. */
+#define GH_JOURNAL_OFF 0
+#define GH_JOURNAL_DETECT 1   /* detections, false positives, latency          */
+#define GH_JOURNAL_VIEWS 3    /* DETECT + dissemination: one census pass/round */
+#define GH_JOURNAL_BINS 64
+typedef struct gh_journal_round {      /* 48 bytes */
+  int32_t round, running, failed, false_failed;
+  int64_t detections, false_detections, stale_views, missing_views;
+} gh_journal_round;
+int gh_journal_enable(void* h, int32_t mode, int64_t log_rounds);
+int gh_journal_read(void* h, int32_t* stop_round, int32_t* start_round,
+                    int32_t* first_round, int32_t* first_detector, int32_t* first_count,
+                    int32_t* last_round, int32_t* det_rounds, int64_t* detectors,
+                    int32_t* fp_rounds, int32_t* forgotten_round, int32_t* known_round,
+                    int64_t* latency_hist, int64_t* forget_hist, int64_t* known_hist);
+int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap,
+                      int64_t* n_total, int64_t* n_out);
+
 /* MergeMemberList (slave/slave.go:414-440) of one received list into the
  * observer's row at the engine's current tick (the last completed round):
  * ids[x] (distinct members) with heartbeats hb[x] >= 0; the remote ts is

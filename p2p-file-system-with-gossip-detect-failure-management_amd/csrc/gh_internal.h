@@ -1108,3 +1108,26 @@ void launch_file_audit(const GhDev& d, int32_t R, const GhFileAudit& o, int32_t 
 #define GH_FS_WGS 1024
 void launch_file_select(const GhDev& d, int32_t R, const uint32_t* abits, int32_t member, int32_t max_working,
                         int32_t* out, unsigned long long* n_out, uint32_t* wgc, hipStream_t s);
+// journal.hip (gh_journal_*; DESIGN.md "Journal"): the per-member record of
+// the detector over time, one entry per local column c < ncol, and what the
+// rounds add up to. Kept apart from GhDev (the kernarg of every round kernel):
+// only k_journal takes it. All sums are integer and reduce across column
+// shards with SUM alone.
+#define GH_JR_SUMS 7  // a log entry's sums: running, failed, false_failed, detections, false_detections,
+                      // stale_views, missing_views
+struct GhJournal {
+  long long *detectors;
+  int32_t *first_count, *det_rounds, *fp_rounds;                          // cleared to 0
+  int32_t *stop_round, *start_round, *first_round, *first_detector;       // cleared to -1
+  int32_t *last_round, *forgotten_round, *known_round;
+  uint8_t *prev_alive;       // alive[] of the previous journaled round (the baseline at first)
+  unsigned long long *hist;  // [3][GH_JOURNAL_BINS]: latency, forget, known
+  unsigned long long *slot;  // [GH_JR_SUMS] this round's log entry, zero on entry (null: no log)
+  unsigned long long *next;  // [GH_JR_SUMS] the next round's, zeroed by this launch (never `slot`)
+};
+// One thread per local column, after launch_finish of round r: cnt / dmin =
+// det_cnt / det_min of D_r, alive = alive[] from this shard's column 0,
+// listed = the census of the table after the round (null: GH_JOURNAL_DETECT),
+// running = the running members of the whole cluster.
+void launch_journal(const GhJournal& j, const int32_t* cnt, const int32_t* dmin, const uint8_t* alive,
+                    const int32_t* listed, int32_t ncol, int32_t r, int32_t running, hipStream_t s);

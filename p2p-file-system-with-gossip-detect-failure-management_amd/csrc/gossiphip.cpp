@@ -153,6 +153,19 @@ struct Engine {
   size_t fa_bytes = 0;
   int fa_lds_n = 512;  // GH_FA_LDS_N: members up to which the audit's workgroups keep load / sole in LDS (A/B; 0: never)
   int fs_ordered = 1;  // GH_FS_ORDERED=0: gh_file_select compacts unordered and sorts on the host (A/B)
+  // gh_journal_* (journal.hip), allocated by gh_journal_enable only. jn_buf:
+  // one member block per column shard (the allgather's slices; one in all for
+  // a single engine or row shards), detectors i64 [ncs] then the ten int32
+  // fields [ncs] each in GhJournal's order. jn_acc: the three histograms, then
+  // the log ring of jn_log + 1 entries of GH_JR_SUMS sums (the spare one is
+  // the entry a launch clears for the next round). jn_cs: the census
+  // accumulators of GH_JOURNAL_VIEWS (gh_census's block layout).
+  int jn_mode = GH_JOURNAL_OFF;
+  int64_t jn_log = 0, jn_total = 0;
+  char *jn_buf = nullptr, *jn_cs = nullptr;
+  uint8_t* jn_prev = nullptr;
+  unsigned long long* jn_acc = nullptr;
+  std::vector<int32_t> jn_rounds;  // the round of each ring entry
   std::string err;
   std::vector<void*> allocs;
 };
@@ -1567,6 +1580,110 @@ int settle_rows(Engine* e, int64_t row0, int64_t n, const GhRound& p) {
   return GH_OK;
 }
 
+// ---- detection journal (journal.hip; DESIGN.md "Journal") ---------------
+constexpr size_t kJnI32 = 10;  // int32 fields of a member's record (after its int64 detectors)
+constexpr size_t kJnHist = 3 * GH_JOURNAL_BINS;
+
+bool jn_gather(const Engine* e) { return !e->rowlay && e->world > 1; }
+size_t jn_blk(const Engine* e) { return (sizeof(int64_t) + kJnI32 * sizeof(int32_t)) * (size_t)e->d.ncs; }
+size_t jn_acc_words(const Engine* e) { return kJnHist + (size_t)(e->jn_log + 1) * GH_JR_SUMS; }
+// gh_census's block: bins and sums u64, then listed, tomb, cmin, hmax, amax
+size_t jn_cs_head(const Engine* e) { return sizeof(uint64_t) * (GH_CENSUS_BINS + (size_t)e->d.ncs); }
+
+// This shard's member block as the kernel's pointers (no log entry selected).
+GhJournal jn_view(const Engine* e) {
+  const size_t ncs = (size_t)e->d.ncs;
+  char* mine = e->jn_buf + (jn_gather(e) ? jn_blk(e) * e->rank : 0);
+  GhJournal j{};
+  j.detectors = reinterpret_cast<long long*>(mine);
+  int32_t* w = reinterpret_cast<int32_t*>(mine + sizeof(int64_t) * ncs);
+  j.first_count = w;
+  j.det_rounds = w + ncs;
+  j.fp_rounds = w + 2 * ncs;
+  j.stop_round = w + 3 * ncs;
+  j.start_round = w + 4 * ncs;
+  j.first_round = w + 5 * ncs;
+  j.first_detector = w + 6 * ncs;
+  j.last_round = w + 7 * ncs;
+  j.forgotten_round = w + 8 * ncs;
+  j.known_round = w + 9 * ncs;
+  j.prev_alive = e->jn_prev;
+  j.hist = e->jn_acc;
+  return j;
+}
+
+void journal_free(Engine* e) {
+  dfree(e, e->jn_buf);
+  dfree(e, e->jn_cs);
+  dfree(e, e->jn_prev);
+  dfree(e, e->jn_acc);
+  e->jn_buf = e->jn_cs = nullptr;
+  e->jn_prev = nullptr;
+  e->jn_acc = nullptr;
+  e->jn_mode = GH_JOURNAL_OFF;
+  e->jn_log = e->jn_total = 0;
+  e->jn_rounds.clear();
+}
+
+// An empty journal whose baseline is the current alive[] (enable, import,
+// init_full). Local work only: every shard clears its own.
+int journal_clear(Engine* e) {
+  if (e->jn_mode == GH_JOURNAL_OFF) return GH_OK;
+  const GhDev& d = e->d;
+  const size_t ncs = (size_t)d.ncs;
+  const GhJournal j = jn_view(e);
+  HIPCHK(e, hipMemsetAsync(j.detectors, 0, (sizeof(int64_t) + 3 * sizeof(int32_t)) * ncs, e->stream));
+  HIPCHK(e, hipMemsetAsync(j.stop_round, 0xFF, 7 * sizeof(int32_t) * ncs, e->stream));
+  HIPCHK(e, hipMemsetAsync(e->jn_prev, 0, ncs, e->stream));
+  if (d.ncol > 0)
+    HIPCHK(e, hipMemcpyAsync(e->jn_prev, e->alive.data() + d.col0, (size_t)d.ncol, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemsetAsync(e->jn_acc, 0, sizeof(uint64_t) * jn_acc_words(e), e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->jn_total = 0;
+  return GH_OK;
+}
+
+// Round r has run and the buffers have flipped: D_r's counts are
+// det_cnt[dcur] (the next round's k_finish clears them), the new table is
+// buffer cur for round r + 1, as gh_census reads it.
+int journal_round(Engine* e, int32_t r) {
+  const GhDev& d = e->d;
+  const size_t ncs = (size_t)d.ncs;
+  const int32_t* listed = nullptr;
+  int32_t running = 0;
+  if (e->jn_mode == GH_JOURNAL_VIEWS) {
+    const size_t head = jn_cs_head(e);
+    GhCensus o;
+    o.hist = reinterpret_cast<unsigned long long*>(e->jn_cs);
+    o.sum = o.hist + GH_CENSUS_BINS;
+    o.listed = reinterpret_cast<int32_t*>(e->jn_cs + head);
+    o.tomb = o.listed + ncs;
+    o.cmin = o.tomb + ncs;
+    o.hmax = o.cmin + ncs;
+    o.amax = o.hmax + ncs;
+    HIPCHK(e, hipMemsetAsync(e->jn_cs, 0, head + sizeof(int32_t) * 2 * ncs, e->stream));
+    HIPCHK(e, hipMemsetAsync(o.cmin, 0xFF, sizeof(int32_t) * 3 * ncs, e->stream));
+    launch_census(d, e->cur, e->round + 1, o, e->stream);
+    HIPCHK(e, hipGetLastError());
+    // column shards: the column's owner holds its whole count; row shards: the sum of the shards' rows
+    if (e->rowlay && e->world > 1) COMMCHK(e, e->comm->allreduce(o.listed, o.listed, ncs, GH_DT_I32, GH_OP_SUM, e->stream));
+    listed = o.listed;
+    for (uint8_t a : e->alive) running += a != 0;
+  }
+  GhJournal j = jn_view(e);
+  if (e->jn_log > 0) {
+    const int64_t P = e->jn_log + 1;
+    unsigned long long* ring = e->jn_acc + kJnHist;
+    j.slot = ring + (e->jn_total % P) * GH_JR_SUMS;
+    j.next = ring + ((e->jn_total + 1) % P) * GH_JR_SUMS;
+    e->jn_rounds[e->jn_total % P] = r;
+  }
+  launch_journal(j, d.det_cnt[e->dcur], d.det_min[e->dcur], d.alive + d.col0, listed, d.ncol, r, running, e->stream);
+  HIPCHK(e, hipGetLastError());
+  e->jn_total++;
+  return GH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1832,7 +1949,7 @@ int gh_import_state(void* h, const int32_t* hb, const int32_t* ts, const uint8_t
   }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  return GH_OK;
+  return journal_clear(e);  // (a journal starts again from the new alive[])
 }
 
 int gh_export_state(void* h, int32_t* hb, int32_t* ts, uint8_t* alive, int64_t row0, int64_t n_rows) {
@@ -1876,7 +1993,7 @@ int gh_init_full(void* h, int32_t hb0, int32_t ts0, int32_t round) {
   }
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  return GH_OK;
+  return journal_clear(e);  // (a journal starts again from the new alive[])
 }
 
 int gh_apply_events(void* h, const gh_event* ev, int64_t n) {
@@ -2101,6 +2218,7 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     e->flags_known = true;
     e->hb_bound = std::min<int64_t>(INT32_MAX, e->hb_bound + 1);
     done++;
+    if (e->jn_mode != GH_JOURNAL_OFF && (rc = journal_round(e, r))) return rc;
     if (busy && q + 1 < rounds) {
       // a quarter of the arena in use on some shard: check and grow after
       // every round (collectively), so only a jump from under 1/4 to over
@@ -2569,6 +2687,119 @@ int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min, in
     if (hb_max && nc > 0) std::memcpy(hb_max + c0, w + 3 * ncs, sizeof(int32_t) * nc);
     if (age_max && nc > 0) std::memcpy(age_max + c0, w + 4 * ncs, sizeof(int32_t) * nc);
     for (int64_t c = 0; hb_min && c < nc; ++c) hb_min[c0 + c] = w[2 * ncs + c] < 0 ? -1 : INT32_MAX - w[2 * ncs + c];
+  }
+  return GH_OK;
+}
+
+// The detection journal (journal.hip): journal_round keeps it inside gh_step.
+// Column shards journal their own columns (a log entry's sums over them): the
+// member blocks are allgathered, the histograms and the log summed, on read.
+// Row shards and one engine hold every column and the same journal.
+int gh_journal_enable(void* h, int32_t mode, int64_t log_rounds) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (mode != GH_JOURNAL_OFF && mode != GH_JOURNAL_DETECT && mode != GH_JOURNAL_VIEWS)
+    return set_err(e, GH_EINVAL, "journal mode");
+  if (log_rounds < 0 || log_rounds > (1 << 20)) return set_err(e, GH_EINVAL, "log_rounds outside 0..2^20");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  journal_free(e);
+  if (mode == GH_JOURNAL_OFF) return GH_OK;
+  e->jn_mode = mode;
+  e->jn_log = log_rounds;
+  const size_t ncs = (size_t)e->d.ncs;
+  int rc;
+  if ((rc = dalloc(e, &e->jn_buf, jn_blk(e) * (jn_gather(e) ? e->world : 1), 0)) ||
+      (rc = dalloc(e, &e->jn_prev, ncs, 0)) || (rc = dalloc(e, &e->jn_acc, jn_acc_words(e), 0)) ||
+      (mode == GH_JOURNAL_VIEWS && (rc = dalloc(e, &e->jn_cs, jn_cs_head(e) + sizeof(int32_t) * 5 * ncs, 0)))) {
+    journal_free(e);
+    return rc;
+  }
+  e->jn_rounds.assign((size_t)log_rounds + 1, 0);
+  return journal_clear(e);
+}
+
+int gh_journal_read(void* h, int32_t* stop_round, int32_t* start_round, int32_t* first_round,
+                    int32_t* first_detector, int32_t* first_count, int32_t* last_round, int32_t* det_rounds,
+                    int64_t* detectors, int32_t* fp_rounds, int32_t* forgotten_round, int32_t* known_round,
+                    int64_t* latency_hist, int64_t* forget_hist, int64_t* known_hist) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (e->jn_mode == GH_JOURNAL_OFF) return set_err(e, GH_EINVAL, "the journal is off");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  const GhDev& d = e->d;
+  const size_t ncs = (size_t)d.ncs, blk = jn_blk(e);
+  const bool gather = jn_gather(e);
+  const int nblk = gather ? e->world : 1;
+  Staging st;
+  int rc;
+  const unsigned long long* hist = e->jn_acc;
+  if (gather) {
+    if ((rc = st.alloc(e, sizeof(uint64_t) * kJnHist))) return rc;
+    COMMCHK(e, e->comm->allgather(e->jn_buf + blk * e->rank, e->jn_buf, blk, e->stream));
+    COMMCHK(e, e->comm->allreduce(e->jn_acc, st.p, kJnHist, GH_DT_U64, GH_OP_SUM, e->stream));
+    hist = st.as<unsigned long long>();
+  }
+  std::vector<char> host(blk * nblk);
+  int64_t hh[kJnHist];
+  HIPCHK(e, hipMemcpyAsync(host.data(), e->jn_buf, host.size(), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(hh, hist, sizeof hh, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (latency_hist) std::memcpy(latency_hist, hh, sizeof(int64_t) * GH_JOURNAL_BINS);
+  if (forget_hist) std::memcpy(forget_hist, hh + GH_JOURNAL_BINS, sizeof(int64_t) * GH_JOURNAL_BINS);
+  if (known_hist) std::memcpy(known_hist, hh + 2 * GH_JOURNAL_BINS, sizeof(int64_t) * GH_JOURNAL_BINS);
+  // the block's int32 fields, in GhJournal's order
+  int32_t* const outs[kJnI32] = {first_count, det_rounds,     fp_rounds,  stop_round,      start_round,
+                                 first_round, first_detector, last_round, forgotten_round, known_round};
+  for (int g = 0; g < nblk; ++g) {
+    const char* b = host.data() + blk * g;
+    const int64_t c0 = gather ? (int64_t)g * d.ncs : 0;
+    const int64_t nc = std::max<int64_t>(0, std::min<int64_t>(d.ncs, e->n - c0));
+    if (nc <= 0) continue;
+    if (detectors) std::memcpy(detectors + c0, b, sizeof(int64_t) * nc);
+    const int32_t* w = reinterpret_cast<const int32_t*>(b + sizeof(int64_t) * ncs);
+    for (size_t f = 0; f < kJnI32; ++f)
+      if (outs[f]) std::memcpy(outs[f] + c0, w + f * ncs, sizeof(int32_t) * nc);
+  }
+  return GH_OK;
+}
+
+int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap, int64_t* n_total, int64_t* n_out) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (e->jn_mode == GH_JOURNAL_OFF) return set_err(e, GH_EINVAL, "the journal is off");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(e, GH_EINVAL, "journal rounds: cap / null buffer");
+  const int64_t k = std::min(std::min(e->jn_total, e->jn_log), cap);
+  if (n_total) *n_total = e->jn_total;
+  if (n_out) *n_out = k;
+  if (k <= 0) return GH_OK;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  const int64_t P = e->jn_log + 1;
+  const size_t words = (size_t)P * GH_JR_SUMS;
+  const unsigned long long* ring = e->jn_acc + kJnHist;
+  Staging st;
+  int rc;
+  if (jn_gather(e)) {  // each shard's entries count its own columns
+    if ((rc = st.alloc(e, sizeof(uint64_t) * words))) return rc;
+    COMMCHK(e, e->comm->allreduce(ring, st.p, words, GH_DT_U64, GH_OP_SUM, e->stream));
+    ring = st.as<unsigned long long>();
+  }
+  std::vector<unsigned long long> host(words);
+  HIPCHK(e, hipMemcpyAsync(host.data(), ring, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const bool views = e->jn_mode == GH_JOURNAL_VIEWS;
+  for (int64_t x = 0; x < k; ++x) {
+    const int64_t slot = (e->jn_total - k + x) % P;
+    const unsigned long long* v = host.data() + slot * GH_JR_SUMS;
+    gh_journal_round& o = out[x];
+    o.round = e->jn_rounds[slot];
+    o.running = (int32_t)v[0];
+    o.failed = (int32_t)v[1];
+    o.false_failed = (int32_t)v[2];
+    o.detections = (int64_t)v[3];
+    o.false_detections = (int64_t)v[4];
+    o.stale_views = views ? (int64_t)v[5] : -1;
+    o.missing_views = views ? (int64_t)v[6] : -1;
   }
   return GH_OK;
 }

@@ -30,10 +30,23 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_DETECT_QUIRK,
                    GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS, GH_ORDER_APPEND, GH_ORDER_ID, GH_REMOVE_ALL, GH_REMOVE_LIST,
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
-                   GH_PEER_RING, Config, PlanEntry)
+                   GH_PEER_RING, Config, PlanEntry,
+                   GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS)
 
-__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "GossipError", "default_config",
-           "comm_unique_id", "Config"]
+__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "Journal", "GossipError", "default_config",
+           "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
+           "GH_JOURNAL_BINS"]
+
+# gh_journal_read, in ABI order: per member id [N] (detectors int64, the rest int32), then the three histograms
+# int64 [GH_JOURNAL_BINS]
+Journal = namedtuple("Journal", "stop_round start_round first_round first_detector first_count last_round "
+                                "det_rounds detectors fp_rounds forgotten_round known_round "
+                                "latency_hist forget_hist known_hist")
+# gh_journal_round as a numpy record (48 bytes)
+JOURNAL_ROUND_DTYPE = np.dtype([("round", np.int32), ("running", np.int32), ("failed", np.int32),
+                                ("false_failed", np.int32), ("detections", np.int64),
+                                ("false_detections", np.int64), ("stale_views", np.int64),
+                                ("missing_views", np.int64)])
 
 # gh_census: per member id [N] (age_hist: [GH_CENSUS_BINS] over every listed cell)
 Census = namedtuple("Census", "listed tombstoned hb_min hb_max hb_sum age_max age_hist")
@@ -346,6 +359,44 @@ class Engine:
         self._chk(self.lib.gh_census(self.h, *[_p(a) for a in out]))
         return out
 
+    def journal_enable(self, mode=GH_JOURNAL_DETECT, log_rounds=0):
+        """Start (or, with GH_JOURNAL_OFF, drop) the detection journal
+        (gh_journal_enable): from now on every round of step() records, on
+        the device, each member's starts, stops, detections and false
+        positives, the detection latencies and, with log_rounds > 0, a log
+        entry of the last log_rounds rounds. GH_JOURNAL_VIEWS also records when
+        every view dropped a stopped member / learnt a running one, for one
+        census pass per round. Any call clears the journal; the baseline is
+        the current alive vector."""
+        self._chk(self.lib.gh_journal_enable(self.h, int(mode), int(log_rounds)))
+
+    def journal(self):
+        """The per-member record and the three latency histograms since
+        journal_enable (gh_journal_read), as a Journal; -1 = never."""
+        n = self.n
+        out = Journal(*[np.empty(n, np.int64 if f == "detectors" else np.int32) for f in Journal._fields[:11]],
+                      *[np.empty(GH_JOURNAL_BINS, np.int64) for _ in range(3)])
+        self._chk(self.lib.gh_journal_read(self.h, *[_p(a) for a in out]))
+        return out
+
+    def journal_rounds(self, cap=None):
+        """The newest (at most cap) entries of the journal's round log,
+        oldest first, as a structured array (JOURNAL_ROUND_DTYPE: round,
+        running, failed, false_failed, detections, false_detections,
+        stale_views, missing_views); gh_journal_rounds."""
+        tot, k = C.c_int64(), C.c_int64()
+        self._chk(self.lib.gh_journal_rounds(self.h, None, 0, C.byref(tot), None))
+        cap = tot.value if cap is None else int(cap)
+        buf = (_abi.JournalRound * max(cap, 1))()
+        self._chk(self.lib.gh_journal_rounds(self.h, buf, cap, C.byref(tot), C.byref(k)))
+        return np.frombuffer(buf, dtype=JOURNAL_ROUND_DTYPE, count=k.value).copy()
+
+    def journal_total(self):
+        """Rounds journaled since journal_enable (the log keeps the last log_rounds of them)."""
+        tot = C.c_int64()
+        self._chk(self.lib.gh_journal_rounds(self.h, None, 0, C.byref(tot), None))
+        return tot.value
+
     def merge_list(self, observer, ids, hb):
         """MergeMemberList (slave/slave.go:414-440) of a received list into
         `observer`'s row now; returns the number of cells changed."""
@@ -632,6 +683,20 @@ class Cluster:
         """Every member's view count, heartbeat spread and age distribution
         over the running members (Engine.census)."""
         return self.engine.census()
+
+    def journal_enable(self, mode=GH_JOURNAL_DETECT, log_rounds=0):
+        """Journal every tick from now on (Engine.journal_enable). Crashes an
+        election causes (log.Fatal) are events like any crash, so they are
+        journaled too."""
+        self.engine.journal_enable(mode, log_rounds)
+
+    def journal(self):
+        """Per member: stop, first detection, false positives, ... (Engine.journal)."""
+        return self.engine.journal()
+
+    def journal_rounds(self, cap=None):
+        """The journal's round log (Engine.journal_rounds)."""
+        return self.engine.journal_rounds(cap)
 
     # wire format of the gossip datagrams (slave/slave.go:365-385, 527-542)
     def datagram(self, member) -> bytes:

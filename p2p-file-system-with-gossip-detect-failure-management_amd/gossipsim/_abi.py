@@ -35,6 +35,8 @@ GH_REMOVE_ALL, GH_REMOVE_LIST = 0, 1
 GH_CENSUS_BINS = 32
 GH_AVAIL_ALIVE = -1
 GH_AUDIT_BINS = 9
+GH_JOURNAL_OFF, GH_JOURNAL_DETECT, GH_JOURNAL_VIEWS = 0, 1, 3
+GH_JOURNAL_BINS = 64
 # gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
 # environment variable GH_<NAME> that gh_create reads)
 KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
@@ -72,6 +74,12 @@ class PlanEntry(C.Structure):
                 ("n_new", C.c_int32), ("status", C.c_int32), ("new_nodes", C.c_int32 * 8)]
 
 
+class JournalRound(C.Structure):
+    """gh_journal_round: one round's log entry of the detection journal."""
+    _fields_ = [(n, C.c_int32) for n in ("round", "running", "failed", "false_failed")] + \
+               [(n, C.c_int64) for n in ("detections", "false_detections", "stale_views", "missing_views")]
+
+
 # (name, restype, argtypes) for every symbol include/gossiphip.h declares.
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 _P = C.POINTER
@@ -91,6 +99,9 @@ SYMBOLS = [
     ("gh_read_detectors", C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     ("gh_lsm", C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _P(_i64)]),
     ("gh_census", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gh_journal_enable", C.c_int, [_vp, _i32, _i64]),
+    ("gh_journal_read", C.c_int, [_vp] + [_vp] * 14),
+    ("gh_journal_rounds", C.c_int, [_vp, _P(JournalRound), _i64, _P(_i64), _P(_i64)]),
     ("gh_merge_list", C.c_int, [_vp, _i32, _vp, _vp, _i64, _P(_i64)]),
     ("gh_put", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     ("gh_put_conflicts", C.c_int, [_vp, _vp, _i64, _i32, _vp]),
