@@ -442,7 +442,10 @@ int gh_set_master(void* h, int32_t master);
  *                      ALL columns (north_star): each round the senders'
  *                      rows that a shard's receivers pull cross shards by
  *                      one alltoallv (ncclAllToAllv), O(N^2 k/G) bytes.
- *                      Pull mode only (ring mode: GH_EINVAL). */
+ *                      Pull and ring mode: in ring mode each sender's owner
+ *                      finds its 3 targets in its own row, the targets are
+ *                      reduced, and the senders' rows travel to their
+ *                      receivers' owners the same way. */
 #define GH_LAYOUT_COLUMNS 0
 #define GH_LAYOUT_ROWS 1
 

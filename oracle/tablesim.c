@@ -191,10 +191,14 @@ int or_import_state(void *h, const int32_t *hb, const int32_t *ts, const uint8_t
   memcpy(s->ts + row0 * s->n, ts, n_rows * s->n * 4);
   memcpy(s->alive + row0, alive, n_rows);
   s->round = round;
+  /* an imported list holds no member twice: the RecentFailList entries kept
+   * beside present members (D7) are the introducer's, and go when its row is
+   * among those written; an import of other rows leaves its lists alone */
+  const int own = s->cfg.introducer >= row0 && s->cfg.introducer < row0 + n_rows;
   for (int32_t c = 0; c < s->n; ++c) {
     s->det_cnt[c] = 0;
     s->det_min[c] = INT_MAX;
-    s->shadow[c] = OR_NO_SHADOW; /* an imported list holds no member twice */
+    if (own) s->shadow[c] = OR_NO_SHADOW;
   }
   memset(s->det_any, 0, s->rows);
   return GH_OK;

@@ -10,20 +10,25 @@ from oracle import philox
 JOIN, LEAVE, CRASH = 1, 2, 3
 
 
-def bootstrap_schedule(n, start=1):
-    """C1-style start: member r-start joins in round r (0 first: the
-    introducer joins through itself, slave/slave.go:288 + :228)."""
-    return {start + c: [(JOIN, c)] for c in range(n)}
+def bootstrap_schedule(n, start=1, introducer=0):
+    """C1-style start: one member joins per round, the introducer first (it
+    joins through itself, slave/slave.go:288 + :228), then the others in ID
+    order."""
+    order = [introducer] + [c for c in range(n) if c != introducer]
+    return {start + k: [(JOIN, c)] for k, c in enumerate(order)}
 
 
-def random_churn(n, rounds, seed, p_crash=0.04, p_leave=0.02, p_join=0.05, start_full=True):
-    """Per-round batches of crash/leave/join events on a seeded stream."""
+def random_churn(n, rounds, seed, p_crash=0.04, p_leave=0.02, p_join=0.05, start_full=True, introducer=0):
+    """Per-round batches of crash/leave/join events on a seeded stream; the
+    introducer is spared."""
     rng = np.random.default_rng(seed)
     alive = np.ones(n, bool) if start_full else np.zeros(n, bool)
     sched = {}
     for r in range(1, rounds + 1):
         ev = []
-        for c in range(1, n):  # keep the introducer alive so joins can happen
+        for c in range(n):
+            if c == introducer:  # keep the introducer alive so joins can happen
+                continue
             u = rng.random()
             if alive[c] and u < p_crash:
                 ev.append((CRASH, c))
@@ -39,9 +44,9 @@ def random_churn(n, rounds, seed, p_crash=0.04, p_leave=0.02, p_join=0.05, start
     return sched
 
 
-def rejoin_churn(n, rounds, seed, p_out=0.06, p_back=0.5):
+def rejoin_churn(n, rounds, seed, p_out=0.06, p_back=0.5, introducer=0):
     """Members leave (or crash) and come back within a few rounds, again and
-    again: the introducer (member 0) still holds the tombstone of a member
+    again: the introducer (spared here) still holds the tombstone of a member
     when it rejoins, so its list holds the member twice (SPEC D7), and a
     later LEAVE, REMOVE or detection meets that double entry."""
     rng = np.random.default_rng(seed)
@@ -49,7 +54,9 @@ def rejoin_churn(n, rounds, seed, p_out=0.06, p_back=0.5):
     sched = {}
     for r in range(1, rounds + 1):
         ev = []
-        for c in range(1, n):
+        for c in range(n):
+            if c == introducer:
+                continue
             u = rng.random()
             if alive[c] and u < p_out:
                 ev.append((LEAVE if rng.random() < 0.6 else CRASH, c))
@@ -62,17 +69,61 @@ def rejoin_churn(n, rounds, seed, p_out=0.06, p_back=0.5):
     return sched
 
 
-def crash_ids(n, frac, seed):
+def crash_ids(n, frac, seed, introducer=0):
     """BASELINE configs: crash `frac` of N, IDs drawn by Philox(seed, CRASH);
-    the introducer/master (0) is excluded."""
+    the introducer/master is excluded."""
     count = max(1, int(round(n * frac)))
-    return philox.sample_distinct(seed, philox.TAG_CRASH, count, n, exclude=(0,))
+    return philox.sample_distinct(seed, philox.TAG_CRASH, count, n, exclude=(introducer,))
+
+
+def introducer_outage(sched, I, stops):
+    """A copy of `sched` with the events `stops` = [(round, kind), ...] added
+    for the introducer I itself: it crashes or leaves, JOINs that arrive while
+    it is down reset their rows but are added nowhere, and its own JOIN
+    restarts it with an empty list (it joins through itself)."""
+    out = {r: list(ev) for r, ev in sched.items()}
+    for r, kind in stops:
+        out.setdefault(r, []).append((kind, I))
+    return out
 
 
 def full_state(n, hb0=2, ts0=0):
     hb = np.full((n, n), hb0, np.int32)
     ts = np.full((n, n), ts0, np.int32)
     alive = np.ones(n, np.uint8)
+    return hb, ts, alive
+
+
+def short_list_state(n, seed, r0, mid=False):
+    """(hb, ts, alive), to import at round r0: every member alive and every
+    row full (hb r0 + 2, ts r0) but the last 16, whose lists hold 0, 1, 2 and
+    3 members, each with and without the row's own entry, twice over (a list
+    of length 0 cannot hold its row, so both of its variants are empty). The
+    other entries of a short row are drawn by `seed` and were last heard of
+    in round 0, so with r0 > T_fail a short row that passes the guard detects
+    them at once and may empty itself after the guard. These are the rows the
+    min_members guard decides differently below 4, and the ring senders whose
+    targets coincide, name the sender itself, or do not exist. With `mid` the
+    8 rows before them hold 4, 5, 6 and 8 members in the same way: the rows a
+    threshold of 7 decides differently from the literal 4."""
+    rng = np.random.default_rng(seed)
+    hb = np.full((n, n), r0 + 2, np.int32)
+    ts = np.full((n, n), r0, np.int32)
+    alive = np.ones(n, np.uint8)
+    shapes = [(ln, own) for ln in (0, 1, 2, 3) for own in (True, False)] * 2
+    if mid:
+        shapes = [(ln, own) for ln in (4, 5, 6, 8) for own in (True, False)] + shapes
+    for k, (ln, own) in enumerate(shapes):
+        i = n - len(shapes) + k
+        others = np.array([c for c in range(n) if c != i])
+        own = own and ln > 0
+        keep = rng.choice(others, ln - int(own), replace=False)
+        hb[i, :] = -1
+        ts[i, :] = 0
+        hb[i, keep] = r0 + 2  # (ts stays 0: unheard of since round 0)
+        if own:
+            hb[i, i] = r0 + 2
+            ts[i, i] = r0
     return hb, ts, alive
 
 
@@ -140,3 +191,19 @@ def export_view(hb, ts, round_, t_cleanup):
         old = (hb == -2) & (now - t > t_cleanup + 1)
         t[old] = now - (t_cleanup + 1)
     return hb, t.astype(np.int32)
+
+
+def shadow_view(sh, round_, t_cleanup):
+    """D7 shadow entries (the ts of the introducer's RecentFailList entry
+    beside a present member, INT32_MIN for none) as export_view presents a
+    tombstone's ts: the engine keeps a tombstone's age saturated at
+    T_cleanup + 1 rounds, which is all cleanFailList (slave/slave.go:490) can
+    tell, and an introducer whose list is under the guard threshold never
+    cleans, so its entries do grow older than that."""
+    none = np.iinfo(np.int32).min
+    t = np.asarray(sh).astype(np.int64)
+    if t_cleanup < 30:
+        now = round_ + 1
+        old = (t != none) & (now - t > t_cleanup + 1)
+        t[old] = now - (t_cleanup + 1)
+    return t.astype(np.int32)

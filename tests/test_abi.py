@@ -86,6 +86,20 @@ def test_remove_list_validation(abi):
     assert lit - base >= 5 * 4096 * 4096 // 8  # two recipient sets + three column bitmaps of N x N bits
 
 
+@pytest.mark.parametrize("kw", [dict(introducer=-1), dict(introducer=64), dict(master=-1), dict(master=64),
+                                dict(min_members=-1), dict(replicas=0), dict(replicas=9)],
+                         ids=lambda kw: "%s=%d" % next(iter(kw.items())))
+def test_config_range_validation(abi, kw):
+    """gh_create refuses an introducer or master outside [0, N), a negative
+    min_members and replicas outside 1..8 before it looks for a device."""
+    from gossipsim import default_config
+    lib = abi.load()
+    h = C.c_void_p()
+    cfg = default_config(64, **kw)
+    assert lib.gh_create(C.byref(cfg), C.byref(h)) == abi.GH_EINVAL
+    assert not h.value
+
+
 def test_no_cpu_fallback(abi):
     """Without a gfx950 device gh_create must fail (GH_ENODEV), never emulate."""
     import torch
