@@ -2220,9 +2220,17 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     done++;
     if (e->jn_mode != GH_JOURNAL_OFF && (rc = journal_round(e, r))) return rc;
     if (busy && q + 1 < rounds) {
-      // a quarter of the arena in use on some shard: check and grow after
-      // every round (collectively), so only a jump from under 1/4 to over
-      // 1/1 in one round can overflow it
+      // more than a quarter of the arena in use on some shard at the call's
+      // start (or at the last of these checks): check after every round and
+      // double the arena once it is more than half full (collectively).
+      // While the checks last, a round overflows it only by taking the use
+      // from at most 1/2 to over 1/1 at once. A call that starts at or under
+      // 1/4 (or whose use fell back there) is not checked again before its
+      // end: a climb of a few segments a round that passes the capacity
+      // inside such a call does overflow it, the call returns GH_ENOMEM and
+      // the state is lost as the header says (split the call, or raise
+      // gh_config.wide_segments;
+      // tests/test_gpu_call_partition.py::test_arena_climb_inside_a_call_quiet_start)
       if ((rc = maybe_grow(e, &busy, true))) return rc;
     }
   }
