@@ -171,6 +171,64 @@ SOLE_N, SOLE_R0 = 2048, 20
 SOLE_CASES = [(2, 1, 0, 0.16), (3, 2, 0, 0.16)]
 
 
+def tail_members(n, bounds=()):
+    """The members whose cells end a piece of the nibble path's geometry at a
+    cluster size n that is no multiple of the 256-member tile: the last
+    member, the first cell of the last 16-cell lane and of the last 8-cell
+    chunk, both sides of the last tile boundary, and both sides of every
+    shard boundary in `bounds` (g * ncs of the column layout, g * nrs of the
+    row layout). Sorted, distinct, the introducer 0 spared."""
+    last = 256 * ((n - 1) // 256)
+    ids = {n - 1, 16 * ((n - 1) // 16), 8 * ((n - 1) // 8), last, last - 1}
+    for b in bounds:
+        ids |= {b - 1, b}
+    return sorted(x for x in ids if 0 < x < n)
+
+
+def shard_bounds(n, world, layout=0):
+    """First member of every shard but the first: columns g * ncs with ncs =
+    ceil(n / world) rounded up to 32 (layout 0), rows g * nrs with nrs =
+    ceil(n / world) (layout 1), as gh_create_sharded lays them out."""
+    per = -(-n // world)
+    if layout == 0:
+        per = -(-per // 32) * 32
+    return [g * per for g in range(1, world) if g * per < n]
+
+
+# The ragged-N runs (test_ragged_scenario.py asserts their preconditions on
+# the oracle, test_gpu_ragged.py runs them): the sizes, each with another
+# tail against the 256-member tile, the 16-cell lane and the 8-cell chunk,
+RAGGED_NS = (250, 263, 520, 1000, 2049)
+RAGGED_ROUNDS, RAGGED_CRASH, RAGGED_REJOIN = 40, 8, 30
+# ... (label, n, world, layout) of the sharded runs (layout 1: row shards),
+RAGGED_SHARDS = [("cols2", 263, 2, 0), ("cols3", 263, 3, 0), ("cols8_n250", 250, 8, 0),
+                 ("rows2", 263, 2, 1), ("rows3", 263, 3, 1), ("rows3_n1000", 1000, 3, 1)]
+# ... and the quirk-detection victims: runs of candidates that end on the
+# row's last list entry, across the 2,048-cell window edge at N = 2,049.
+# Crashed at round 8 like the wave, each is first detected by the few rows
+# that pulled from it in its last round, one candidate per row, so no choice
+# of victims makes quirk detection differ from canonical; crashed at round 1,
+# before their first heartbeat, every row holds them at ts 0 and detects the
+# whole run in round 17, where the quirk skips every second candidate.
+RAGGED_QUIRK = {263: [254, 255, 256, 261, 262], 2049: [2046, 2047, 2048]}
+RAGGED_QUIRK_CRASH = (8, 1)
+
+
+def ragged_cfg(k=4, detect_mode=0):
+    return dict(fanout=k, seed=0x5EED0C10, t_fail=16, t_cleanup=16, detect_mode=detect_mode)
+
+
+def ragged_wave(n, victims=None, rejoin=True, crash=RAGGED_CRASH):
+    """`victims` (tail_members(n) by default) crash at round 8; with `rejoin`
+    the last member joins again at round 30, after its REMOVE: its column's
+    base jump makes lane jobs of the last, partial lane."""
+    victims = tail_members(n) if victims is None else victims
+    sched = {crash: [(CRASH, int(c)) for c in victims]}
+    if rejoin:
+        sched[RAGGED_REJOIN] = [(JOIN, n - 1)]
+    return sched
+
+
 def masked(hb, ts):
     """ts of absent cells carries no meaning in the list model (listsim keeps
     no Member for them); compare it only where hb != -1."""
