@@ -290,6 +290,48 @@ int gh_journal_read(void* h, int32_t* stop_round, int32_t* start_round,
 int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap,
                       int64_t* n_total, int64_t* n_out);
 
+/* Lossy gossip links: per-member send / receive drop rates of the gossip
+ * messages. They model the one transport of the reference that loses
+ * messages, the UDP datagrams a member's list travels in (slave/slave.go:
+ * 527-542); JOIN, LEAVE, REMOVE and gh_merge_list stay reliable (SPEC D9).
+ * State: thresholds in units of 2^-32, out[m] for member m's sends and in[m]
+ * for its receives. hit(thr, w) = thr == GH_LOSS_ALWAYS || w < thr: 0
+ * (GH_LOSS_NEVER) never drops, GH_LOSS_ALWAYS always does. B(a, r, blk) = the
+ * Philox4x32-10 block of counter (a, r, 'LINK' = 0x4C494E4B, blk) under the
+ * engine's seed; r = the round being run (SPEC §2 step 6a).
+ *   Pull mode: receiver i's draw t < k of peer p, drawn exactly as without
+ *   loss, is a message iff it is valid without loss (p alive and active, i in
+ *   p's snapshot list and not REMOVE'd at p). The message is dropped iff
+ *   hit(out[p], B(i, r, t)[0]) || hit(in[i], B(i, r, t)[1]); p contributes iff
+ *   it is not. Two draws of one peer are two messages.
+ *   Ring mode (either list order): sender s, slot q in 0..2, target g =
+ *   targets[3 s + q] is a message iff g exists and is alive; it is dropped iff
+ *   hit(out[s], B(s, r, q)[0]) || hit(in[g], B(s, r, q)[1]).
+ * Nothing else changes: the peer and placement draws are untouched, and with
+ * loss off or both arrays all zero every table, statistic and diagnostic is
+ * bit-identical.
+ * gh_set_loss: out_q32 / in_q32 [N] by member id; one NULL pointer = that side
+ * all zero; both NULL switch loss off and free its state. Every call zeroes
+ * the counters. It takes effect from the next round run and persists across
+ * gh_step, gh_import_state and gh_init_full (configuration, not table state).
+ * gh_get_loss: *enabled, and the two arrays [N] (all 0 with loss off); any
+ * output may be NULL. gh_loss_stats: *sent = the gossip messages and *dropped
+ * = the dropped ones since the last gh_set_loss (either may be NULL);
+ * GH_EINVAL with loss off. A NULL handle returns GH_EINVAL from all three
+ * before any device is touched.
+ * Off is the default: gh_create allocates nothing for it, gh_footprint and
+ * gh_memory_info at creation do not include it, and gh_step launches nothing
+ * new in either state (the kernels that build the inboxes take one uniform
+ * branch). Enabled it holds 8 N + 16 bytes per shard (the arrays are
+ * replicated). Additive under ABI 7. On a sharded handle all three calls are
+ * collective: every rank passes the same arguments and gets the global
+ * result. */
+#define GH_LOSS_NEVER 0u
+#define GH_LOSS_ALWAYS 0xFFFFFFFFu
+int gh_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32);
+int gh_get_loss(void* h, int32_t* enabled, uint32_t* out_q32, uint32_t* in_q32);
+int gh_loss_stats(void* h, int64_t* sent, int64_t* dropped);
+
 /* MergeMemberList (slave/slave.go:414-440) of one received list into the
  * observer's row at the engine's current tick (the last completed round):
  * ids[x] (distinct members) with heartbeats hb[x] >= 0; the remote ts is

@@ -221,6 +221,7 @@
 #define GH_PLANE_MIN_N 16384     // the sender plane from this many members on
 #define GH_TAG_PEER 0x50454552u
 #define GH_TAG_PLACE 0x504C4143u
+#define GH_TAG_LINK 0x4C494E4Bu  // 'LINK': the per-message loss draws (gh_link_drop)
 #define GH_MAX_DRAWS (1u << 20)
 
 enum {
@@ -236,8 +237,9 @@ enum {
 };
 
 // Philox4x32-10 (Salmon et al. SC'11), the same stream as SPEC.md §2/§6.
-__host__ __device__ inline uint32_t gh_philox_word(uint64_t seed, uint32_t a, uint32_t b,
-                                                   uint32_t tag, uint32_t blk, int t) {
+// The whole 4-word block of counter (a, b, tag, blk).
+__host__ __device__ inline void gh_philox_block(uint64_t seed, uint32_t a, uint32_t b, uint32_t tag, uint32_t blk,
+                                                uint32_t o[4]) {
   uint32_t c0 = a, c1 = b, c2 = tag, c3 = blk;
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
@@ -255,7 +257,15 @@ __host__ __device__ inline uint32_t gh_philox_word(uint64_t seed, uint32_t a, ui
     c0 = n0;
     c2 = n2;
   }
-  const uint32_t o[4] = {c0, c1, c2, c3};
+  o[0] = c0;
+  o[1] = c1;
+  o[2] = c2;
+  o[3] = c3;
+}
+__host__ __device__ inline uint32_t gh_philox_word(uint64_t seed, uint32_t a, uint32_t b,
+                                                   uint32_t tag, uint32_t blk, int t) {
+  uint32_t o[4];
+  gh_philox_block(seed, a, b, tag, blk, o);
   return o[t & 3];
 }
 
@@ -398,6 +408,12 @@ struct GhDev {
   int32_t* vlog;
   int32_t *nd;      // [0..1] local |D| per parity, [2..3] dlist fill, [4] join adds, [5] list merges
   int32_t *inbox_beg, *inbox_cnt, *inbox, *inbox_fill, *targets;
+  // lossy links (gh_set_loss; null: off, the default -- no gossip message is
+  // dropped and nothing is drawn): [0..3] the counters sent, dropped as two
+  // uint64, then the thresholds in units of 2^-32 of every member's sends
+  // [n] and receives [n], replicated on every shard. Read only by the kernels
+  // that decide whether a message arrives (gh_link_drop)
+  uint32_t *link;
   int32_t *ring;    // ring mode: [world][n][2] (local snapshot count, local position of the sender)
   uint16_t *rcnt;   // ring mode: [ld/tw][n] snapshot-list members per (tile, sender row)
   uint32_t *rbits;  // gathered presence bitmaps of some rows: [world][nr][ncsw]
@@ -910,6 +926,29 @@ struct GhRound {
   int32_t gpo;          // row layout: this round's ghost rows carry only their sender plane (the
                         // 16-bit codes arrive after k_round, before k_round_slow, if any segment needs them)
 };
+
+// ---- lossy links (SPEC §2 step 6a) ----------------------------------------
+// A threshold thr (units of 2^-32) against a draw w: 0 never, GH_LOSS_ALWAYS
+// always.
+__host__ __device__ __forceinline__ bool gh_link_hit(uint32_t thr, uint32_t w) {
+  return thr == GH_LOSS_ALWAYS || w < thr;
+}
+__device__ __forceinline__ unsigned long long* gh_link_counters(const GhDev& d) {
+  return reinterpret_cast<unsigned long long*>(d.link);
+}
+// The gossip message `sender` -> `receiver` of round p.r is lost: block
+// B(a, r, blk) = Philox(seed; a, r, GH_TAG_LINK, blk), word 0 against the
+// sender's out threshold, word 1 against the receiver's in threshold. Pull
+// mode: a = the receiver, blk = its draw; ring mode: a = the sender, blk = its
+// target slot. Loss off (d.link null): one uniform branch, no Philox.
+__device__ __forceinline__ bool gh_link_drop(const GhDev& d, const GhRound& p, uint32_t a, uint32_t blk, int64_t sender,
+                                             int64_t receiver) {
+  if (!d.link) return false;
+  uint32_t w[4];
+  gh_philox_block(p.seed, a, (uint32_t)p.r, GH_TAG_LINK, blk, w);
+  const uint32_t* thr = d.link + 4;
+  return gh_link_hit(thr[sender], w[0]) || gh_link_hit(thr[p.n + receiver], w[1]);
+}
 
 // ---- launchers (kernels in round.hip / events.hip / place.hip) ----------
 // round.hip

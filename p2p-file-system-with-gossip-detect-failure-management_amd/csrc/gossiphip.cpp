@@ -2812,6 +2812,70 @@ int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap, int64_t* n_to
   return GH_OK;
 }
 
+// Lossy links (SPEC §2 step 6a; gh_internal.h GhDev.link, gh_link_drop): the
+// thresholds live on the device only, replicated on every shard, so setting
+// them needs no exchange; the counters are summed over the shards on read
+// (each message is counted on one).
+int gh_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  GhDev& d = e->d;
+  if (!out_q32 && !in_q32) {
+    dfree(e, d.link);
+    d.link = nullptr;
+    return GH_OK;
+  }
+  const size_t n = (size_t)e->n;
+  int rc;
+  if (!d.link && (rc = dalloc(e, &d.link, 4 + 2 * n, 0))) return rc;
+  HIPCHK(e, hipMemsetAsync(d.link, 0, sizeof(uint32_t) * (4 + 2 * n), e->stream));
+  if (out_q32) HIPCHK(e, hipMemcpyAsync(d.link + 4, out_q32, sizeof(uint32_t) * n, hipMemcpyHostToDevice, e->stream));
+  if (in_q32) HIPCHK(e, hipMemcpyAsync(d.link + 4 + n, in_q32, sizeof(uint32_t) * n, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_get_loss(void* h, int32_t* enabled, uint32_t* out_q32, uint32_t* in_q32) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  const GhDev& d = e->d;
+  const size_t n = (size_t)e->n;
+  if (enabled) *enabled = d.link != nullptr;
+  if (!d.link) {
+    if (out_q32) std::memset(out_q32, 0, sizeof(uint32_t) * n);
+    if (in_q32) std::memset(in_q32, 0, sizeof(uint32_t) * n);
+    return GH_OK;
+  }
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  if (out_q32) HIPCHK(e, hipMemcpyAsync(out_q32, d.link + 4, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->stream));
+  if (in_q32) HIPCHK(e, hipMemcpyAsync(in_q32, d.link + 4 + n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_loss_stats(void* h, int64_t* sent, int64_t* dropped) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (!e->d.link) return set_err(e, GH_EINVAL, "loss is off");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  const void* src = e->d.link;
+  Staging st;
+  int rc;
+  if (e->world > 1) {
+    if ((rc = st.alloc(e, 2 * sizeof(uint64_t)))) return rc;
+    COMMCHK(e, e->comm->allreduce(src, st.p, 2, GH_DT_U64, GH_OP_SUM, e->stream));
+    src = st.p;
+  }
+  int64_t v[2];
+  HIPCHK(e, hipMemcpyAsync(v, src, sizeof v, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (sent) *sent = v[0];
+  if (dropped) *dropped = v[1];
+  return GH_OK;
+}
+
 // gh_file_audit / gh_file_select (files.hip). Scratch layout: 16 u64 (the 11
 // audit counters; [12] the select count), load [n], sole [n] (contiguous: one
 // SUM allreduce, one copy out), the availability and master bitmaps, the

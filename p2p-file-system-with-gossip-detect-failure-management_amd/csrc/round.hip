@@ -7,7 +7,9 @@
 //                  need nothing else; the few undecided rows get an exact
 //                  post-REMOVE count (summed over ranks when sharded).
 //   k_peers_pull   per receiver column: k Philox peers, kept iff the sender is
-//                  active, alive and lists the receiver (slave/slave.go:527-542).
+//                  active, alive and lists the receiver (slave/slave.go:527-542)
+//                  and, under gh_set_loss, the message is not lost (gh_link_drop;
+//                  the same in k_peers_rows and the ring's k_inbox_count / _fill).
 //   k_ring_*       reference ring topology (slave/slave.go:512-524): per-(tile,row)
 //                  snapshot counts, positions, targets + inbox CSR.
 //   k_quirk_*      quirk-mode detection pre-pass (SPEC §4).
@@ -84,6 +86,27 @@ __device__ __forceinline__ void count_active(const GhDev& d, bool a) {
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_act, __popcll(m));
   __syncthreads();
   if (d.rank == 0 && threadIdx.x == 0 && s_act) atomicAdd(&d.stats[ST_ACTIVE_ROWS], (unsigned long long)s_act);
+}
+
+// Lossy links (d.link set): this thread's gossip messages and the dropped
+// ones into the engine's counters, one atomic each per workgroup. Every thread
+// of a 256-thread workgroup calls it; here = this shard counts them (a
+// message is counted once in the cluster).
+__device__ __forceinline__ void count_links(const GhDev& d, int sent, int dropped, bool here) {
+  __shared__ int s_lk[2];
+  if (threadIdx.x < 2) s_lk[threadIdx.x] = 0;
+  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) {
+    sent += __shfl_xor(sent, o);
+    dropped += __shfl_xor(dropped, o);
+  }
+  if ((threadIdx.x & 63) == 0 && sent) {
+    atomicAdd(&s_lk[0], sent);
+    if (dropped) atomicAdd(&s_lk[1], dropped);
+  }
+  __syncthreads();
+  if (here && threadIdx.x < 2 && s_lk[threadIdx.x])
+    atomicAdd(gh_link_counters(d) + threadIdx.x, (unsigned long long)s_lk[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void k_active_pre(GhDev d, int cur, int dcur, GhRound p) {
@@ -197,6 +220,11 @@ __global__ __launch_bounds__(256) void k_peers_pull(GhDev d, int cur, int dcur, 
       if (ok && dbit(d.dbits, t) && gh_rm_at(d, dcur, t, s)) ok = false;
     }
   }
+  if (d.link) {  // lossy links: a valid draw is a message, a dropped one counts as no draw from here on
+    const bool msg = ok;
+    if (msg && gh_link_drop(d, p, (uint32_t)i, (uint32_t)q, s, i)) ok = false;
+    count_links(d, msg, msg && !ok, true);  // (each receiver's draws are decided on one shard)
+  }
   const unsigned long long m = __ballot(ok);
   const int lane = threadIdx.x & 63;
   const uint32_t grp = (uint32_t)(m >> (lane & ~7)) & 0xFFu;  // this receiver's valid draws
@@ -253,21 +281,31 @@ __global__ __launch_bounds__(256) void k_inbox_bits(GhDev d, GhRound p) {
 // so a SUM over shards is the validity of every draw.
 __global__ __launch_bounds__(256) void k_peers_rows(GhDev d, int cur, int dcur, GhRound p) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  const bool ib = dbit(d.dbits, i);
-  for (int q = 0; q < p.k; ++q) {
-    int v = 0;
-    if (d.alive[i] && p.n >= 2) {
-      const uint32_t u = gh_philox_word(p.seed, (uint32_t)i, (uint32_t)p.r, GH_TAG_PEER, (uint32_t)(q >> 2), q & 3);
-      const uint32_t w = (uint32_t)(((uint64_t)u * (uint64_t)(p.n - 1)) >> 32);
-      const int s = (int)w + ((int64_t)w >= i);
-      if (gh_owned(d, s) && d.alive[s] && d.active[s]) {
-        const GhCell c = gh_get(d, cur, s, i, p.r);
-        v = c.x >= 0 && !c.f && !(ib && gh_rm_at(d, dcur, i, s));
+  int sent = 0, dropped = 0;  // lossy links: the messages this shard's senders decide
+  if (i < p.n) {
+    const bool ib = dbit(d.dbits, i);
+    for (int q = 0; q < p.k; ++q) {
+      int v = 0;
+      if (d.alive[i] && p.n >= 2) {
+        const uint32_t u = gh_philox_word(p.seed, (uint32_t)i, (uint32_t)p.r, GH_TAG_PEER, (uint32_t)(q >> 2), q & 3);
+        const uint32_t w = (uint32_t)(((uint64_t)u * (uint64_t)(p.n - 1)) >> 32);
+        const int s = (int)w + ((int64_t)w >= i);
+        if (gh_owned(d, s) && d.alive[s] && d.active[s]) {
+          const GhCell c = gh_get(d, cur, s, i, p.r);
+          v = c.x >= 0 && !c.f && !(ib && gh_rm_at(d, dcur, i, s));
+          if (v && d.link) {
+            sent++;
+            if (gh_link_drop(d, p, (uint32_t)i, (uint32_t)q, s, i)) {
+              v = 0;
+              dropped++;
+            }
+          }
+        }
       }
+      d.pvf[i * p.k + q] = v;
     }
-    d.pvf[i * p.k + q] = v;
   }
+  if (d.link) count_links(d, sent, dropped, true);
 }
 
 // Row layout: every receiver's inbox from the summed validity of its draws
@@ -549,11 +587,22 @@ __global__ __launch_bounds__(256) void k_ring_select(GhDev d, int cur, int dcur,
 
 __global__ __launch_bounds__(256) void k_inbox_count(GhDev d, GhRound p) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= p.n) return;
-  for (int q = 0; q < 3; ++q) {
-    const int t = d.targets[(int64_t)s * 3 + q];
-    if (t >= 0 && d.alive[t]) atomicAdd(&d.inbox_cnt[t], 1);
+  int sent = 0, dropped = 0;  // lossy links
+  if (s < p.n) {
+    for (int q = 0; q < 3; ++q) {
+      const int t = d.targets[(int64_t)s * 3 + q];
+      if (t >= 0 && d.alive[t]) {
+        if (gh_link_drop(d, p, (uint32_t)s, (uint32_t)q, s, t)) {
+          dropped++;
+        } else {
+          atomicAdd(&d.inbox_cnt[t], 1);
+        }
+        sent++;
+      }
+    }
   }
+  // every shard builds every inbox: rank 0 counts, as for ST_RING_EMPTY
+  if (d.link) count_links(d, sent, dropped, d.rank == 0);
 }
 
 // Exclusive scan of inbox_cnt -> inbox_beg; one 1024-thread workgroup. Each
@@ -614,7 +663,7 @@ __global__ __launch_bounds__(256) void k_inbox_fill(GhDev d, GhRound p) {
   if (d.alive[s] && (d.active[s] || d.inbox_cnt[s] || !d.stab[p.r & 1][s])) d.aq[0] = 1;  // row s is not quiet
   for (int q = 0; q < 3; ++q) {
     const int t = d.targets[(int64_t)s * 3 + q];
-    if (t >= 0 && d.alive[t]) {
+    if (t >= 0 && d.alive[t] && !gh_link_drop(d, p, (uint32_t)s, (uint32_t)q, s, t)) {  // (k_inbox_count's rule)
       const int pos = atomicAdd(&d.inbox_fill[t], 1);
       d.inbox[d.inbox_beg[t] + pos] = s;
     }

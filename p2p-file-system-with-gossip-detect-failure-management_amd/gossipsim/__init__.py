@@ -31,11 +31,12 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_LAYOUT_COLUMNS, GH_LAYOUT_ROWS, GH_ORDER_APPEND, GH_ORDER_ID, GH_REMOVE_ALL, GH_REMOVE_LIST,
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
                    GH_PEER_RING, Config, PlanEntry,
-                   GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS)
+                   GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS,
+                   GH_LOSS_ALWAYS, GH_LOSS_NEVER)
 
 __all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "Journal", "GossipError", "default_config",
            "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
-           "GH_JOURNAL_BINS"]
+           "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS"]
 
 # gh_journal_read, in ABI order: per member id [N] (detectors int64, the rest int32), then the three histograms
 # int64 [GH_JOURNAL_BINS]
@@ -397,6 +398,50 @@ class Engine:
         self._chk(self.lib.gh_journal_rounds(self.h, None, 0, C.byref(tot), None))
         return tot.value
 
+    def _loss_q32(self, p):
+        """One side of set_loss as uint32 [N] thresholds in units of 2^-32
+        (None stays None: that side all zero)."""
+        if p is None:
+            return None
+        a = np.asarray(p)
+        if a.dtype == np.uint32:
+            q = a
+        else:
+            a = a.astype(np.float64)
+            if ((a < 0) | (a > 1)).any():
+                raise ValueError("a drop rate lies in [0, 1]")
+            q = np.minimum(np.round(a * 2.0 ** 32), 0xFFFFFFFF).astype(np.uint32)
+        if q.ndim == 0:
+            q = np.full(self.n, q, np.uint32)
+        if q.shape != (self.n,):
+            raise ValueError("per-member drop rates are [N]")
+        return np.ascontiguousarray(q)
+
+    def set_loss(self, out=None, inbound=None):
+        """Lossy gossip links (gh_set_loss): from the next round on a gossip
+        message of sender s to receiver g is dropped with probability out[s]
+        on its way out or inbound[g] on its way in (slave/slave.go:527-542 sends
+        its lists as UDP datagrams). Each side is a float in [0, 1], [N]
+        floats, or raw uint32 [N] thresholds in units of 2^-32 (0xFFFFFFFF:
+        always); None = never. Both None switch loss off. JOIN, LEAVE, REMOVE
+        and merge_list stay reliable. Every call zeroes loss_stats()."""
+        o, i = self._loss_q32(out), self._loss_q32(inbound)
+        self._chk(self.lib.gh_set_loss(self.h, None if o is None else _p(o), None if i is None else _p(i)))
+
+    def loss(self):
+        """(enabled, out, inbound): the thresholds as uint32 [N] (gh_get_loss; zeros with loss off)."""
+        en = C.c_int32()
+        o, i = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
+        self._chk(self.lib.gh_get_loss(self.h, C.byref(en), _p(o), _p(i)))
+        return bool(en.value), o, i
+
+    def loss_stats(self):
+        """(sent, dropped): the gossip messages and the dropped ones since the
+        last set_loss (gh_loss_stats); GossipError(GH_EINVAL) with loss off."""
+        s, d = C.c_int64(), C.c_int64()
+        self._chk(self.lib.gh_loss_stats(self.h, C.byref(s), C.byref(d)))
+        return s.value, d.value
+
     def merge_list(self, observer, ids, hb):
         """MergeMemberList (slave/slave.go:414-440) of a received list into
         `observer`'s row now; returns the number of cells changed."""
@@ -697,6 +742,15 @@ class Cluster:
     def journal_rounds(self, cap=None):
         """The journal's round log (Engine.journal_rounds)."""
         return self.engine.journal_rounds(cap)
+
+    def set_loss(self, out=None, inbound=None):
+        """Per-member drop rates of the gossip datagrams from the next tick
+        on (Engine.set_loss); JOIN, LEAVE and REMOVE stay reliable."""
+        self.engine.set_loss(out, inbound)
+
+    def loss_stats(self):
+        """(sent, dropped) gossip messages since set_loss (Engine.loss_stats)."""
+        return self.engine.loss_stats()
 
     # wire format of the gossip datagrams (slave/slave.go:365-385, 527-542)
     def datagram(self, member) -> bytes:
