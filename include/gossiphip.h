@@ -332,6 +332,68 @@ int gh_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32);
 int gh_get_loss(void* h, int32_t* enabled, uint32_t* out_q32, uint32_t* in_q32);
 int gh_loss_stats(void* h, int64_t* sent, int64_t* dropped);
 
+/* Network partitions (SPEC §2 step 6b): every member m is on side[m] in
+ * [0, GH_PART_SIDES); reach(a, b) = side[a] == side[b]. Between members that
+ * do not reach each other nothing is delivered: gossip, REMOVE, LEAVE and
+ * JOIN. (gh_set_loss cannot express this: its REMOVEs, LEAVEs and JOINs stay
+ * reliable, SPEC D9.)
+ *   Gossip: a pull draw (receiver i, draw t, peer p) that is valid, or a ring
+ *   message (sender s, slot q, target g existing and alive), is CUT iff the
+ *   two do not reach each other. A cut message does not merge, adds 1 to the
+ *   counter `cut`, and is no message for gh_set_loss: neither sent nor
+ *   dropped, no LINK block drawn. The peer draws do not change.
+ *   REMOVE: the recipients are fixed by the sides in force in the round of
+ *   the detection. With n_j(c) = the detectors of c on row j's side and
+ *   m_j(c) the lowest of them, row j applies REMOVE(c) in the next round iff
+ *   it is alive, n_j(c) > 0 and not (n_j(c) == 1 and m_j(c) == j): rule D4 per
+ *   side. det_cnt / det_min, gh_read_failed, gh_read_detectors, the stats and
+ *   the journal stay global. A call between two rounds does not change who
+ *   receives the REMOVE set already pending.
+ *   Events, by the sides in force in the round that runs them: LEAVE(c)
+ *   reaches j iff reach(c, j); a joiner's process starts fresh on any side;
+ *   its JOIN reaches the introducer I iff reach(c, I); I's broadcast reaches j
+ *   iff reach(I, j).
+ *   Not gated: gh_merge_list, the file calls, gh_vote_scan, gh_rebuild_meta,
+ *   gh_census, gh_file_audit.
+ * After a heal, two sides that have dropped each other never re-merge by
+ * gossip (a member only sends to members of its own list, and only lists it
+ * is a member of reach it); they re-merge only through a JOIN.
+ * gh_set_partition: side [N] by member id; a value outside [0, GH_PART_SIDES)
+ * returns GH_EINVAL and changes nothing. NULL heals (every member to side 0);
+ * the state stays allocated until gh_destroy. Every call zeroes `cut`. The
+ * sides are configuration: they persist across gh_step, gh_import_state and
+ * gh_init_full and take effect from the next round run. With all sides equal
+ * every table, statistic, list and diagnostic equals a never-partitioned
+ * engine's, and cut == 0.
+ * NOT SUPPORTED, GH_EINVAL: a sharded handle (world > 1) and a GH_REMOVE_LIST
+ * engine (both out of scope so far); never anywhere else.
+ * gh_get_partition: *armed, and side [N] (all 0 when not armed); any output
+ * may be NULL. gh_partition_stats: *cut since the last gh_set_partition;
+ * GH_EINVAL when the engine is not armed. A NULL handle returns GH_EINVAL from
+ * all three before any device is touched.
+ * Before the first gh_set_partition nothing is allocated or launched
+ * (gh_footprint and gh_memory_info at creation do not change; the inbox
+ * kernels take one uniform branch on a null pointer). The first call ARMS the
+ * engine: it allocates side[] and three bitmaps of ld * ceil(N / 32) words
+ * (the recipients of two REMOVE sets and the detectors of a sweep; 3 x 512 MiB
+ * at N = 65,536) and switches REMOVE delivery to per-(row, member) recipients
+ * read from a bitmap, as a GH_REMOVE_LIST engine's. From then on a round with
+ * a detection also builds the detectors' bitmaps and the recipients of D_r
+ * (csrc/remove.hip k_part_recv). Additive under ABI 7.
+ * Measured on a MI355X at N = 65,536, k = 4 pull (profiles/partition_time.json):
+ * never armed 2.14 ms per round (the parent commit: 2.10-2.21 over three
+ * processes); armed with every member on side 0, 2.18 ms; the two REMOVE
+ * rounds of a 1 % crash 7.9 ms each (never armed 2.5 ms, a GH_REMOVE_LIST
+ * engine 9.0 ms) and its detection rounds 5.2 ms (2.3 / 7.4 ms). A real split
+ * is a heavier workload: with the members split even / odd the rounds stay at
+ * 2.1 ms for 9 rounds and reach 17-36 ms by rounds 10-15. That jump was not
+ * profiled; the supposed cause is the views that lag once half the draws are
+ * cut, which the round kernels take off their fast path. */
+#define GH_PART_SIDES 64
+int gh_set_partition(void* h, const int32_t* side);
+int gh_get_partition(void* h, int32_t* armed, int32_t* side);
+int gh_partition_stats(void* h, int64_t* cut);
+
 /* MergeMemberList (slave/slave.go:414-440) of one received list into the
  * observer's row at the engine's current tick (the last completed round):
  * ids[x] (distinct members) with heartbeats hb[x] >= 0; the remote ts is

@@ -178,6 +178,7 @@ struct OpLeave {
   __device__ GhCell operator()(int64_t j, int64_t c, const GhCell& v, uint32_t* t) const {
     const int q = d.colq[c];
     if (q < 0 || !d.alive[j] || d.col0 + c == j || !gh_gbit(d, d.rbits, nl, q, j)) return v;
+    if (gh_part_cut(d, d.col0 + c, j)) return v;  // the LEAVE does not cross a partition (SPEC §5)
     if (v.x >= 0 && j == shadow_row && d.shadow[c] != GH_NO_SHADOW) {
       // the introducer holds c in RecentFailList too (D7): that entry, its
       // ts, is the tombstone; nothing is appended (:278-281)
@@ -229,6 +230,7 @@ struct OpJoinBcast {
   __device__ void flush(const uint32_t* t) const { atomicAdd(&d.stats[ST_MERGED], (unsigned long long)t[0]); }
   __device__ GhCell operator()(int64_t j, int64_t c, const GhCell& v, uint32_t* t) const {
     if (c >= d.ncol || j == I || !d.alive[j] || !gh_gbit(d, d.rbits, 1, 0, j)) return v;
+    if (gh_part_cut(d, I, j)) return v;  // the broadcast does not cross a partition (SPEC §5)
     const GhCell m = gh_get(d, cur, I, c, p.r);
     if (m.x < 0) return v;
     if (v.x >= GH_ABSENT && m.x > v.x) {

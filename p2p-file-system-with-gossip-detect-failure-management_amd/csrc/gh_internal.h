@@ -386,7 +386,12 @@ struct GhDev {
   // REMOVE(c). Built after each detection round (remove.hip) from column
   // bitmaps over the rows that ran the sweep: cdet (the row detected the
   // member), csurv (listed and not detected), clst (listed; self excluded)
-  // and their counts ccnt [0, ld) survivors, [ld, 2 ld) listed, [2 ld] rows
+  // and their counts ccnt [0, ld) survivors, [ld, 2 ld) listed, [2 ld] rows.
+  // rlist = the recipients come from rcv (gh_rm_at reads the bitmap): a
+  // GH_REMOVE_LIST engine, whose rule is the reference's list rule, and an
+  // engine armed by gh_set_partition, whose rule is D4 per side (k_part_recv;
+  // it holds rcv, cdet and ccnt only). Which rule fills rcv is the host's
+  // choice (gossiphip.cpp Engine.rm_ref / d.side)
   int32_t rlist;
   int64_t nw;       // words of a column bitmap over the rows, ceil(n / 32)
   uint32_t *rcv[2];
@@ -414,6 +419,13 @@ struct GhDev {
   // [n] and receives [n], replicated on every shard. Read only by the kernels
   // that decide whether a message arrives (gh_link_drop)
   uint32_t *link;
+  // network partition (gh_set_partition; null: never armed -- nothing is cut
+  // and nothing below is read): side[m] in [0, GH_PART_SIDES) per member,
+  // [n]; the counter `cut` is the uint64 in the two words before it
+  // (gh_part_counter). Read by the kernels that accept a gossip message
+  // (gh_part_cut, before gh_link_drop), by LEAVE / JOIN delivery (events.hip)
+  // and by k_part_recv (remove.hip)
+  int32_t *side;
   int32_t *ring;    // ring mode: [world][n][2] (local snapshot count, local position of the sender)
   uint16_t *rcnt;   // ring mode: [ld/tw][n] snapshot-list members per (tile, sender row)
   uint32_t *rbits;  // gathered presence bitmaps of some rows: [world][nr][ncsw]
@@ -950,6 +962,17 @@ __device__ __forceinline__ bool gh_link_drop(const GhDev& d, const GhRound& p, u
   return gh_link_hit(thr[sender], w[0]) || gh_link_hit(thr[p.n + receiver], w[1]);
 }
 
+// ---- network partition (SPEC §2 step 6b) -----------------------------------
+// A message from member a to member b is cut: they are on different sides.
+// Never armed (d.side null): one uniform branch.
+__device__ __forceinline__ bool gh_part_cut(const GhDev& d, int64_t a, int64_t b) {
+  if (!d.side) return false;
+  return d.side[a] != d.side[b];
+}
+__host__ __device__ __forceinline__ unsigned long long* gh_part_counter(const GhDev& d) {
+  return reinterpret_cast<unsigned long long*>(d.side - 2);
+}
+
 // ---- launchers (kernels in round.hip / events.hip / place.hip) ----------
 // round.hip
 // Row j receives REMOVE(c) of the REMOVE set of parity dcur (c in that set):
@@ -998,6 +1021,13 @@ void launch_finish(const GhDev& d, int dcur, const GhRound& p, hipStream_t s);
 // launch_finish) and the recipients of D_r (after it); remove.hip
 void launch_rm_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s);
 void launch_rm_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s);
+// gh_set_partition (armed engines): the detectors' column bitmaps alone
+// (cdet; before launch_finish), the recipients of D_r by rule D4 per side
+// (after it), and, on arming, the recipients of the pending set of parity
+// dcur by rule D4
+void launch_part_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s);
+void launch_part_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s);
+void launch_part_fill(const GhDev& d, int dcur, const GhRound& p, hipStream_t s);
 // base[cur ^ 1] from buffer cur (member c's own heartbeat - GH_BASE_LAG),
 // |D_{r-1}| next to the local counts, empty slow list
 void launch_base(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s);

@@ -143,6 +143,15 @@ struct Engine {
   // |D| of the last round as read at the end of gh_step (one engine; -1
   // unknown): a first round with a REMOVE pending launches IN 6 on a full grid
   int32_t last_nd = -1;
+  // GH_REMOVE_LIST: rcv is filled by the reference's list rule (remove.hip
+  // k_rm_cols / k_rm_recv). d.rlist alone says only that the recipients come
+  // from rcv, which an engine armed by gh_set_partition sets too
+  bool rm_ref = false;
+  // gh_set_partition: armed by the first call (d.side, rcv, cdet and ccnt are
+  // allocated then and stay until gh_destroy); host copy of side[] (the
+  // joiners the introducer hears, process_events)
+  bool part = false;
+  std::vector<int32_t> side_h;
   // gh_census accumulators: one block per column shard (the allgather's
   // slices), one in all for a single engine or row shards
   char* cs_buf = nullptr;
@@ -963,6 +972,14 @@ int process_events(Engine* e, int32_t r) {
   }
   if ((rc = upload_alive(e))) return rc;
   const int32_t I = e->cfg.introducer;
+  if (e->part && I >= 0 && I < e->n) {
+    // a JOIN reaches the introducer only from its own side (SPEC §5; the
+    // joiner's process has started all the same)
+    std::vector<int32_t> heard;
+    for (int32_t c : joiners)
+      if (e->side_h[c] == e->side_h[I]) heard.push_back(c);
+    joiners.swap(heard);
+  }
   if (!joiners.empty() && I >= 0 && I < e->n && e->alive[I]) {
     if ((rc = upload(e, e->ev_buf, joiners))) return rc;
     launch_join_add(e->d, e->cur, e->ev_buf, (int32_t)joiners.size(), I, p, e->stream);
@@ -1240,7 +1257,8 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   d.world = world;
   d.tsa = cfg->t_cleanup < GH_TSAT_T ? cfg->t_cleanup + 1 : 0;
   d.toff = gh_tier_toff(cfg->t_cleanup);
-  d.rlist = cfg->remove_mode == GH_REMOVE_LIST;
+  e->rm_ref = cfg->remove_mode == GH_REMOVE_LIST;
+  d.rlist = e->rm_ref;  // (gh_set_partition sets it too: recipients from rcv)
   // every shard sizes (and grows) its arena from the same segment count, the
   // largest over the shards, so the grow and lose decisions are collective
   // (ghost rows' wide segments take arena slots of the current buffer too)
@@ -2207,9 +2225,13 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     }
     // the reference's REMOVE recipients of D_r: the sweep's column bitmaps
     // (needs D_{r-1}, before k_finish replaces it), then per member of D_r
-    if (e->d.rlist) launch_rm_cols(e->d, e->cur, e->dcur, p, e->stream);
+    // (an armed engine, gh_set_partition: the detectors' bitmaps alone, then
+    // rule D4 per side)
+    if (e->rm_ref) launch_rm_cols(e->d, e->cur, e->dcur, p, e->stream);
+    if (e->part) launch_part_cols(e->d, e->cur, e->dcur, p, e->stream);
     launch_finish(e->d, e->dcur, p, e->stream);
-    if (e->d.rlist) launch_rm_recv(e->d, e->dcur ^ 1, p, e->stream);
+    if (e->rm_ref) launch_rm_recv(e->d, e->dcur ^ 1, p, e->stream);
+    if (e->part) launch_part_recv(e->d, e->dcur ^ 1, p, e->stream);
     HIPCHK(e, hipGetLastError());
     e->cur ^= 1;
     e->dcur ^= 1;
@@ -2852,6 +2874,84 @@ int gh_get_loss(void* h, int32_t* enabled, uint32_t* out_q32, uint32_t* in_q32) 
   if (out_q32) HIPCHK(e, hipMemcpyAsync(out_q32, d.link + 4, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->stream));
   if (in_q32) HIPCHK(e, hipMemcpyAsync(in_q32, d.link + 4 + n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+// Network partition (SPEC §2 step 6b; gh_internal.h GhDev.side, gh_part_cut,
+// remove.hip k_part_recv). The first call arms the engine: it allocates side[]
+// with its counter and the recipient bitmaps, switches REMOVE delivery to
+// bitmap recipients (d.rlist) and, when a REMOVE set is pending, fills its
+// recipients by rule D4, so the round that delivers it is unchanged.
+int gh_set_partition(void* h, const int32_t* side) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (e->world > 1) return set_err(e, GH_EINVAL, "gh_set_partition: sharded handles are not supported");
+  if (e->rm_ref) return set_err(e, GH_EINVAL, "gh_set_partition: GH_REMOVE_LIST engines are not supported");
+  const size_t n = (size_t)e->n;
+  if (side)
+    for (size_t m = 0; m < n; ++m)
+      if (side[m] < 0 || side[m] >= GH_PART_SIDES) return set_err(e, GH_EINVAL, "gh_set_partition: side out of range");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  GhDev& d = e->d;
+  if (!e->part) {
+    GhDev nd = d;  // armed only when every allocation succeeded
+    int32_t* buf = nullptr;
+    nd.nw = ((int64_t)e->n + 31) / 32;
+    const size_t words = (size_t)e->ld * nd.nw;
+    if ((rc = dalloc(e, &buf, n + 2, 0)) || (rc = dalloc(e, &nd.rcv[0], words, 0)) ||
+        (rc = dalloc(e, &nd.rcv[1], words, 0)) || (rc = dalloc(e, &nd.cdet, words, 0)) ||
+        (rc = dalloc(e, &nd.ccnt, 2 * (size_t)e->ld + 2, 0))) {
+      dfree(e, buf);
+      dfree(e, nd.rcv[0]);
+      dfree(e, nd.rcv[1]);
+      dfree(e, nd.cdet);
+      return rc;
+    }
+    nd.side = buf + 2;
+    nd.rlist = 1;
+    d = nd;
+    e->part = true;
+    e->side_h.assign(n, 0);
+    // the pending REMOVE set (parity dcur) was detected with no sides
+    launch_part_fill(d, e->dcur, round_params(e, e->round + 1), e->stream);
+    HIPCHK(e, hipGetLastError());
+  }
+  HIPCHK(e, hipMemsetAsync(d.side - 2, 0, sizeof(int32_t) * (n + 2), e->stream));  // cut = 0, every side 0
+  if (side) {
+    HIPCHK(e, hipMemcpyAsync(d.side, side, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+    e->side_h.assign(side, side + n);
+  } else {
+    e->side_h.assign(n, 0);
+  }
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_get_partition(void* h, int32_t* armed, int32_t* side) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (armed) *armed = e->part;
+  if (side) {
+    if (e->part)
+      std::copy(e->side_h.begin(), e->side_h.end(), side);
+    else
+      std::memset(side, 0, sizeof(int32_t) * (size_t)e->n);
+  }
+  return GH_OK;
+}
+
+int gh_partition_stats(void* h, int64_t* cut) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (!e->part) return set_err(e, GH_EINVAL, "the engine is not armed (gh_set_partition)");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int64_t v = 0;
+  HIPCHK(e, hipMemcpyAsync(&v, gh_part_counter(e->d), sizeof v, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (cut) *cut = v;
   return GH_OK;
 }
 

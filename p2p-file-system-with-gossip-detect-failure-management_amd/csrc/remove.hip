@@ -38,7 +38,10 @@ __global__ __launch_bounds__(256) void k_rm_any(GhDev d, int dnew, GhRound p) {
 }
 
 // One workgroup per 256 local columns x 256 rows: thread (chunk k, group g)
-// reads 8 columns of 32 rows and writes their 24 bitmap words.
+// reads 8 columns of 32 rows and writes their 24 bitmap words. DET_ONLY (an
+// engine armed by gh_set_partition): det(x) alone, the 8 words of cdet; csurv,
+// clst and the counts are not allocated there.
+template <bool DET_ONLY>
 __global__ __launch_bounds__(256) void k_rm_cols(GhDev d, int cur, int dcur, GhRound p) {
   if (d.ccnt[2 * p.ld + 1] == 0) return;
   __shared__ int s_surv[256], s_lst[256], s_rows;
@@ -112,13 +115,18 @@ __global__ __launch_bounds__(256) void k_rm_cols(GhDev d, int cur, int dcur, GhR
       const int64_t o = (c + j) * d.nw + w;
       if (w < d.nw) {
         d.cdet[o] = wd[j];
-        d.csurv[o] = ws[j];
-        d.clst[o] = wl[j];
+        if constexpr (!DET_ONLY) {
+          d.csurv[o] = ws[j];
+          d.clst[o] = wl[j];
+        }
       }
-      atomicAdd(&s_surv[8 * k + j], __popc(ws[j]));
-      atomicAdd(&s_lst[8 * k + j], __popc(wl[j]));
+      if constexpr (!DET_ONLY) {
+        atomicAdd(&s_surv[8 * k + j], __popc(ws[j]));
+        atomicAdd(&s_lst[8 * k + j], __popc(wl[j]));
+      }
     }
   }
+  if constexpr (DET_ONLY) return;  // (no barrier below is skipped by part of a workgroup: all return here)
   if (k == 0 && cb == 0) atomicAdd(&s_rows, rows);
   __syncthreads();
   const int64_t cc = (int64_t)cb * 256 + threadIdx.x;
@@ -192,13 +200,94 @@ __global__ __launch_bounds__(256) void k_rm_recv(GhDev d, int dnew, GhRound p) {
   }
 }
 
+// ---- network partition (gh_set_partition; SPEC §2 step 6b) ----------------
+// REMOVE(c) of D_r goes from each detector to the rows of its own side, itself
+// excluded: with n_j(c) = the detectors of c on row j's side and m_j(c) the
+// lowest of them, row j receives it iff n_j(c) > 0 and not (n_j(c) == 1 and
+// m_j(c) == j) -- rule D4 per side. One workgroup per member c of D_r
+// (grid-stride): pass 1 walks the set bits of det(c) (cdet, this round's
+// sweep) into a count and a minimum per side in LDS; pass 2 writes
+// rcv[dnew][c], a word per 32 receivers. Rows at or past n get no bit; side[]
+// is read below n only.
+__global__ __launch_bounds__(256) void k_part_recv(GhDev d, int dnew, GhRound p) {
+  __shared__ int s_cnt[GH_PART_SIDES], s_min[GH_PART_SIDES];
+  const int nd = d.nd[2 + dnew];
+  for (int q = blockIdx.x; q < nd; q += gridDim.x) {
+    const int64_t c = d.dlist[(int64_t)dnew * p.ld + q];
+    if (c < 0 || c >= d.ncol) continue;  // (a padded column is never detected; uniform)
+    if (threadIdx.x < GH_PART_SIDES) {
+      s_cnt[threadIdx.x] = 0;
+      s_min[threadIdx.x] = INT_MAX;
+    }
+    __syncthreads();
+    const uint32_t* dcol = d.cdet + c * d.nw;
+    for (int64_t w = threadIdx.x; w < d.nw; w += 256) {
+      for (uint32_t v = dcol[w]; v; v &= v - 1u) {
+        const int64_t i = 32 * w + __builtin_ctz(v);
+        if (i >= p.n) break;
+        const int sd = d.side[i] & (GH_PART_SIDES - 1);
+        atomicAdd(&s_cnt[sd], 1);
+        atomicMin(&s_min[sd], (int)i);
+      }
+    }
+    __syncthreads();
+    for (int64_t w = threadIdx.x; w < d.nw; w += 256) {
+      uint32_t out = 0;
+      for (int b = 0; b < 32; ++b) {
+        const int64_t j = 32 * w + b;
+        if (j >= p.n) break;
+        const int sd = d.side[j] & (GH_PART_SIDES - 1);
+        const int nj = s_cnt[sd];
+        out |= (uint32_t)(nj > 0 && !(nj == 1 && s_min[sd] == j)) << b;
+      }
+      d.rcv[dnew][c * d.nw + w] = out;
+    }
+    __syncthreads();  // the LDS tables before the next member
+  }
+}
+
+// On arming while a REMOVE set is pending (parity dcur, detected before any
+// side existed): its recipients by rule D4 -- every row below n but a sole
+// detector.
+__global__ __launch_bounds__(256) void k_part_fill(GhDev d, int dcur, GhRound p) {
+  const int nd = d.nd[2 + dcur];
+  for (int q = blockIdx.x; q < nd; q += gridDim.x) {
+    const int64_t c = d.dlist[(int64_t)dcur * p.ld + q];
+    if (c < 0 || c >= d.ncol) continue;
+    const int64_t sole = d.det_cnt[dcur][c] == 1 ? d.det_min[dcur][c] : -1;
+    for (int64_t w = threadIdx.x; w < d.nw; w += 256) {
+      const int64_t left = p.n - 32 * w;  // rows of this word below n (>= 1)
+      uint32_t out = left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u;
+      if (sole >= 32 * w && sole < 32 * w + 32) out &= ~(1u << (sole & 31));
+      d.rcv[dcur][c * d.nw + w] = out;
+    }
+  }
+}
+
 }  // namespace
+
+void launch_part_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s) {
+  (void)hipMemsetAsync(d.ccnt, 0, sizeof(int32_t) * (2 * p.ld + 2), s);
+  hipLaunchKernelGGL(k_rm_any, dim3(1), dim3(256), 0, s, d, dcur ^ 1, p);
+  const int64_t nrb = (p.n + 255) / 256;
+  hipLaunchKernelGGL(k_rm_cols<true>, dim3((unsigned)(((p.ld + 255) / 256) * nrb)), dim3(256), 0, s, d, cur, dcur, p);
+}
+
+void launch_part_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s) {
+  hipLaunchKernelGGL(k_part_recv, dim3((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, p.n))), dim3(256), 0, s, d,
+                     dnew, p);
+}
+
+void launch_part_fill(const GhDev& d, int dcur, const GhRound& p, hipStream_t s) {
+  hipLaunchKernelGGL(k_part_fill, dim3((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, p.n))), dim3(256), 0, s, d,
+                     dcur, p);
+}
 
 void launch_rm_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s) {
   (void)hipMemsetAsync(d.ccnt, 0, sizeof(int32_t) * (2 * p.ld + 2), s);
   hipLaunchKernelGGL(k_rm_any, dim3(1), dim3(256), 0, s, d, dcur ^ 1, p);
   const int64_t nrb = (p.n + 255) / 256;
-  hipLaunchKernelGGL(k_rm_cols, dim3((unsigned)(((p.ld + 255) / 256) * nrb)), dim3(256), 0, s, d, cur, dcur, p);
+  hipLaunchKernelGGL(k_rm_cols<false>, dim3((unsigned)(((p.ld + 255) / 256) * nrb)), dim3(256), 0, s, d, cur, dcur, p);
 }
 
 void launch_rm_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s) {

@@ -109,6 +109,19 @@ __device__ __forceinline__ void count_links(const GhDev& d, int sent, int droppe
     atomicAdd(gh_link_counters(d) + threadIdx.x, (unsigned long long)s_lk[threadIdx.x]);
 }
 
+// Network partition (d.side set): this thread's cut gossip messages into the
+// engine's counter, one atomic per workgroup. Every thread of a 256-thread
+// workgroup calls it.
+__device__ __forceinline__ void count_cut(const GhDev& d, int cut, bool here) {
+  __shared__ int s_cut;
+  if (threadIdx.x == 0) s_cut = 0;
+  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) cut += __shfl_xor(cut, o);
+  if ((threadIdx.x & 63) == 0 && cut) atomicAdd(&s_cut, cut);
+  __syncthreads();
+  if (here && threadIdx.x == 0 && s_cut) atomicAdd(gh_part_counter(d), (unsigned long long)s_cut);
+}
+
 __global__ __launch_bounds__(256) void k_active_pre(GhDev d, int cur, int dcur, GhRound p) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -219,6 +232,11 @@ __global__ __launch_bounds__(256) void k_peers_pull(GhDev d, int cur, int dcur, 
       }
       if (ok && dbit(d.dbits, t) && gh_rm_at(d, dcur, t, s)) ok = false;
     }
+  }
+  if (d.side) {  // partition: a valid draw from the other side is cut, and no message for the loss below
+    const bool cut = ok && d.side[s] != d.side[i];
+    if (cut) ok = false;
+    count_cut(d, cut, true);
   }
   if (d.link) {  // lossy links: a valid draw is a message, a dropped one counts as no draw from here on
     const bool msg = ok;
@@ -588,10 +606,15 @@ __global__ __launch_bounds__(256) void k_ring_select(GhDev d, int cur, int dcur,
 __global__ __launch_bounds__(256) void k_inbox_count(GhDev d, GhRound p) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   int sent = 0, dropped = 0;  // lossy links
+  int cut = 0;                // partition
   if (s < p.n) {
     for (int q = 0; q < 3; ++q) {
       const int t = d.targets[(int64_t)s * 3 + q];
       if (t >= 0 && d.alive[t]) {
+        if (gh_part_cut(d, s, t)) {  // (no message: neither sent nor dropped)
+          cut++;
+          continue;
+        }
         if (gh_link_drop(d, p, (uint32_t)s, (uint32_t)q, s, t)) {
           dropped++;
         } else {
@@ -603,6 +626,7 @@ __global__ __launch_bounds__(256) void k_inbox_count(GhDev d, GhRound p) {
   }
   // every shard builds every inbox: rank 0 counts, as for ST_RING_EMPTY
   if (d.link) count_links(d, sent, dropped, d.rank == 0);
+  if (d.side) count_cut(d, cut, d.rank == 0);
 }
 
 // Exclusive scan of inbox_cnt -> inbox_beg; one 1024-thread workgroup. Each
@@ -663,7 +687,8 @@ __global__ __launch_bounds__(256) void k_inbox_fill(GhDev d, GhRound p) {
   if (d.alive[s] && (d.active[s] || d.inbox_cnt[s] || !d.stab[p.r & 1][s])) d.aq[0] = 1;  // row s is not quiet
   for (int q = 0; q < 3; ++q) {
     const int t = d.targets[(int64_t)s * 3 + q];
-    if (t >= 0 && d.alive[t] && !gh_link_drop(d, p, (uint32_t)s, (uint32_t)q, s, t)) {  // (k_inbox_count's rule)
+    if (t >= 0 && d.alive[t] && !gh_part_cut(d, s, t) &&
+        !gh_link_drop(d, p, (uint32_t)s, (uint32_t)q, s, t)) {  // (k_inbox_count's rule)
       const int pos = atomicAdd(&d.inbox_fill[t], 1);
       d.inbox[d.inbox_beg[t] + pos] = s;
     }

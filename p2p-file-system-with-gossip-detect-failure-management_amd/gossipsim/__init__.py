@@ -32,11 +32,11 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
                    GH_PEER_RING, Config, PlanEntry,
                    GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS,
-                   GH_LOSS_ALWAYS, GH_LOSS_NEVER)
+                   GH_LOSS_ALWAYS, GH_LOSS_NEVER, GH_PART_SIDES)
 
 __all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "Journal", "GossipError", "default_config",
            "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
-           "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS"]
+           "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS", "GH_PART_SIDES"]
 
 # gh_journal_read, in ABI order: per member id [N] (detectors int64, the rest int32), then the three histograms
 # int64 [GH_JOURNAL_BINS]
@@ -442,6 +442,41 @@ class Engine:
         self._chk(self.lib.gh_loss_stats(self.h, C.byref(s), C.byref(d)))
         return s.value, d.value
 
+    def set_partition(self, side=None):
+        """A network partition (gh_set_partition): side is [N] ints in
+        [0, GH_PART_SIDES) by member id, and from the next round on nothing is
+        delivered between members on different sides: gossip, REMOVE, LEAVE,
+        JOIN. None heals (every member on side 0). The first call arms the
+        engine (recipient bitmaps of ~3 N^2 / 8 bytes). Every call zeroes
+        partition_stats(). GossipError(GH_EINVAL) for a value out of range, on
+        a sharded engine and on a GH_REMOVE_LIST engine. After a heal, sides
+        that have dropped each other re-merge only through a JOIN."""
+        if side is None:
+            self._chk(self.lib.gh_set_partition(self.h, None))
+            return
+        a = np.asarray(side)
+        if a.shape != (self.n,) or a.dtype.kind not in "iu":
+            raise ValueError("side is [N] integers")
+        a64 = a.astype(np.int64)
+        # (values int32 cannot hold are out of range too: the engine refuses them as it does -1)
+        q = np.ascontiguousarray(np.where((a64 < 0) | (a64 > 0x7FFFFFFF), -1, a64).astype(np.int32))
+        self._chk(self.lib.gh_set_partition(self.h, _p(q)))
+
+    def partition(self):
+        """(armed, side): side int32 [N] (gh_get_partition; zeros when not armed)."""
+        armed = C.c_int32()
+        side = np.empty(self.n, np.int32)
+        self._chk(self.lib.gh_get_partition(self.h, C.byref(armed), _p(side)))
+        return bool(armed.value), side
+
+    def partition_stats(self):
+        """cut: the gossip messages cut by the partition since the last
+        set_partition (gh_partition_stats); GossipError(GH_EINVAL) when the
+        engine is not armed."""
+        cut = C.c_int64()
+        self._chk(self.lib.gh_partition_stats(self.h, C.byref(cut)))
+        return cut.value
+
     def merge_list(self, observer, ids, hb):
         """MergeMemberList (slave/slave.go:414-440) of a received list into
         `observer`'s row now; returns the number of cells changed."""
@@ -751,6 +786,21 @@ class Cluster:
     def loss_stats(self):
         """(sent, dropped) gossip messages since set_loss (Engine.loss_stats)."""
         return self.engine.loss_stats()
+
+    def set_partition(self, side=None):
+        """Split the cluster from the next tick on (Engine.set_partition):
+        gossip, REMOVE, LEAVE and JOIN stop between members on different
+        sides; None heals. With elect=True: ValueError (the election's RPCs
+        across a split are not modelled)."""
+        if self.elect:
+            raise ValueError("partitions are not modelled with elect=True")
+        self.engine.set_partition(side)
+
+    def partition_stats(self):
+        """Gossip messages cut since set_partition (Engine.partition_stats)."""
+        if self.elect:
+            raise ValueError("partitions are not modelled with elect=True")
+        return self.engine.partition_stats()
 
     # wire format of the gossip datagrams (slave/slave.go:365-385, 527-542)
     def datagram(self, member) -> bytes:
