@@ -293,7 +293,8 @@ int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap,
 /* Lossy gossip links: per-member send / receive drop rates of the gossip
  * messages. They model the one transport of the reference that loses
  * messages, the UDP datagrams a member's list travels in (slave/slave.go:
- * 527-542); JOIN, LEAVE, REMOVE and gh_merge_list stay reliable (SPEC D9).
+ * 527-542); JOIN, LEAVE and REMOVE stay reliable unless gh_set_control_loss
+ * (below) opts them in; gh_merge_list always is (SPEC D9).
  * State: thresholds in units of 2^-32, out[m] for member m's sends and in[m]
  * for its receives. hit(thr, w) = thr == GH_LOSS_ALWAYS || w < thr: 0
  * (GH_LOSS_NEVER) never drops, GH_LOSS_ALWAYS always does. B(a, r, blk) = the
@@ -393,6 +394,57 @@ int gh_loss_stats(void* h, int64_t* sent, int64_t* dropped);
 int gh_set_partition(void* h, const int32_t* side);
 int gh_get_partition(void* h, int32_t* armed, int32_t* side);
 int gh_partition_stats(void* h, int64_t* cut);
+
+/* Lossy control messages (SPEC §2 step 6c, §5, D9): which of the control
+ * messages cross the lossy links of gh_set_loss. `kinds` is a mask of
+ * GH_CTL_REMOVE, GH_CTL_LEAVE and GH_CTL_JOIN (the JOIN to the introducer and
+ * the introducer's broadcast); the default, 0, is none and is the engine before
+ * this call existed. It acts only while gh_set_loss is on, with that call's
+ * out[] / in[] thresholds and hit(). W(tag; a, r, b) = the Philox4x32-10 block
+ * of counter (a, r, tag, b) under the engine's seed, r = the round being run;
+ * word 0 is tested against the sender's out threshold, word 1 against the
+ * receiver's in threshold. A message cut by a partition is no message: neither
+ * counted nor drawn. Each decision is a pure function of its counter.
+ *   REMOVE: det(c) = the rows that detected c in round r; E_j(c) = the
+ *   detectors i != j with reach(i, j), whose Remove(c) messages row j. Message
+ *   (i, j, c) draws Philox(K; i, j, 'CRMV' = 0x43524D56, 0) under the key K =
+ *   words 0, 1 of W('CRMV'; c, r, 0), and is dropped iff hit(out[i], w0) ||
+ *   hit(in[j], w1). Row j applies REMOVE(c) in round r + 1 iff it is alive
+ *   then and some message of E_j(c) was not dropped. The thresholds, kinds and
+ *   sides of round r decide; later calls do not change a pending set. det_cnt
+ *   / det_min, gh_read_failed, gh_read_detectors, the stats and the journal
+ *   stay global.
+ *   LEAVE(c) to j (SPEC §5's conditions and reach(c, j)): dropped by
+ *   W('LEAV' = 0x4C454156; c, r, j) against out[c], in[j].
+ *   JOIN of c (c != I, I alive, reach(c, I)): dropped by W('JOIN' =
+ *   0x4A4F494E; c, r, I) against out[c], in[I]; the joiner's process restarts
+ *   whatever happens, and the introducer adds (and in append order appends)
+ *   only the joiners it heard. Its broadcast to j: dropped by W('BCST' =
+ *   0x42435354; I, r, j) against out[I], in[j]. A joiner c == I is local.
+ * gh_set_control_loss: kinds outside 0..7 returns GH_EINVAL. Configuration: it
+ * persists across gh_step, gh_import_state and gh_init_full and takes effect
+ * from the next round run. With GH_CTL_REMOVE on an engine never armed it arms
+ * the engine exactly as gh_set_partition(NULL) would (same allocations, every
+ * member on side 0, a pending REMOVE set filled by rule D4); on an armed engine
+ * sides and `cut` are left alone; without GH_CTL_REMOVE nothing is armed. With
+ * loss off, or both threshold arrays all zero, every table, statistic, list and
+ * diagnostic is bit-identical to kinds = 0. Every call zeroes the counters, and
+ * so does gh_set_loss.
+ * gh_control_loss_stats: out8 = remove_pairs (the (j, c) with E_j(c) non-empty
+ * and j alive as round r ran), remove_missed (those with every message
+ * dropped), leave_sent, leave_dropped, join_sent, join_dropped, bcast_sent,
+ * bcast_dropped. REMOVE counts pairs, not messages: only "did any arrive" is
+ * observable. GH_EINVAL until gh_set_control_loss has been called once.
+ * NOT SUPPORTED, GH_EINVAL: a sharded handle (world > 1) and a GH_REMOVE_LIST
+ * engine. A NULL handle returns GH_EINVAL from all three before any device is
+ * touched. Before the first call nothing is allocated or launched (gh_footprint
+ * and gh_memory_info do not change). Additive under ABI 7. */
+#define GH_CTL_REMOVE 1
+#define GH_CTL_LEAVE 2
+#define GH_CTL_JOIN 4
+int gh_set_control_loss(void* h, int32_t kinds);
+int gh_get_control_loss(void* h, int32_t* kinds);
+int gh_control_loss_stats(void* h, int64_t* out8);
 
 /* MergeMemberList (slave/slave.go:414-440) of one received list into the
  * observer's row at the engine's current tick (the last completed round):

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void k_seg(GhDev d, int buf, SegSet set, const
   const int64_t total = set.count();
   // the ops' counters, summed per wave and added once (one global atomic
   // per cell serialised a 1% LEAVE wave's 43 M tombstones: 0.5 s)
-  uint32_t tal[2] = {0u, 0u};
+  // (tal[2], tal[3]: a lossy control message and its drop, gh_ctl_drop)
+  uint32_t tal[4] = {0u, 0u, 0u, 0u};
   for (int64_t s0 = wave * RPW; s0 < total; s0 += nw * RPW) {
     const int64_t sid = s0 + sub;
     const bool valid = sid < total;
@@ -132,8 +133,10 @@ __global__ __launch_bounds__(256) void k_seg(GhDev d, int buf, SegSet set, const
     for (int o = 32; o > 0; o >>= 1) {
       tal[0] += __shfl_xor(tal[0], o);
       tal[1] += __shfl_xor(tal[1], o);
+      tal[2] += __shfl_xor(tal[2], o);
+      tal[3] += __shfl_xor(tal[3], o);
     }
-    if (lane == 0 && (tal[0] | tal[1])) op.flush(tal);
+    if (lane == 0 && (tal[0] | tal[1] | tal[2])) op.flush(tal);
   }
 }
 
@@ -175,10 +178,14 @@ struct OpLeave {
   GhDev d;
   int32_t nl;
   int32_t shadow_row;  // GhRound.shadow_row
+  GhRound p;
   __device__ GhCell operator()(int64_t j, int64_t c, const GhCell& v, uint32_t* t) const {
     const int q = d.colq[c];
     if (q < 0 || !d.alive[j] || d.col0 + c == j || !gh_gbit(d, d.rbits, nl, q, j)) return v;
     if (gh_part_cut(d, d.col0 + c, j)) return v;  // the LEAVE does not cross a partition (SPEC §5)
+    // ... and may be lost on the way (SPEC §2 step 6c); this cell is the message
+    if (gh_ctl_drop(d, p, GH_CTL_LEAVE, GH_TAG_LEAV, (uint32_t)(d.col0 + c), (uint32_t)j, d.col0 + c, j, t + 2, true))
+      return v;
     if (v.x >= 0 && j == shadow_row && d.shadow[c] != GH_NO_SHADOW) {
       // the introducer holds c in RecentFailList too (D7): that entry, its
       // ts, is the tombstone; nothing is appended (:278-281)
@@ -197,6 +204,8 @@ struct OpLeave {
   __device__ void flush(const uint32_t* t) const {
     if (t[0]) atomicAdd(&d.stats[ST_TOMBSTONED], (unsigned long long)t[0]);
     if (t[1]) atomicAdd(&d.stats[ST_REMOVE_UNKNOWN], (unsigned long long)t[1]);
+    if (t[2]) atomicAdd(&d.ctl[2], (unsigned long long)t[2]);  // leave_sent, leave_dropped
+    if (t[3]) atomicAdd(&d.ctl[3], (unsigned long long)t[3]);
   }
 };
 
@@ -231,6 +240,10 @@ struct OpJoinBcast {
   __device__ GhCell operator()(int64_t j, int64_t c, const GhCell& v, uint32_t* t) const {
     if (c >= d.ncol || j == I || !d.alive[j] || !gh_gbit(d, d.rbits, 1, 0, j)) return v;
     if (gh_part_cut(d, I, j)) return v;  // the broadcast does not cross a partition (SPEC §5)
+    // ... and may be lost on the way (SPEC §2 step 6c): one message per row,
+    // drawn and counted once by k_bcast_drop, so every cell of the row reads
+    // the same decision
+    if (d.ctl && (d.ctl_kinds & GH_CTL_JOIN) && gh_ctl_rowdrop(d)[j]) return v;
     const GhCell m = gh_get(d, cur, I, c, p.r);
     if (m.x < 0) return v;
     if (v.x >= GH_ABSENT && m.x > v.x) {
@@ -240,6 +253,30 @@ struct OpJoinBcast {
     return v;
   }
 };
+
+// The introducer's broadcast over lossy links (GH_CTL_JOIN): one thread per
+// row j decides whether I's message to j exists (OpJoinBcast's conditions) and
+// is dropped, W('BCST'; I, r, j), into gh_ctl_rowdrop[j]; the messages and the
+// dropped ones are summed per wave. Gated like the broadcast itself (nd[4]).
+__global__ __launch_bounds__(256) void k_bcast_drop(GhDev d, int32_t I, GhRound p) {
+  if (d.nd[4] == 0) return;
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t tal[2] = {0u, 0u};
+  if (j < p.n) {
+    bool drop = false;
+    if (j != I && d.alive[j] && gh_gbit(d, d.rbits, 1, 0, j) && !gh_part_cut(d, I, j))
+      drop = gh_ctl_drop(d, p, GH_CTL_JOIN, GH_TAG_BCST, (uint32_t)I, (uint32_t)j, I, j, tal, true);
+    gh_ctl_rowdrop(d)[j] = drop;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    tal[0] += __shfl_xor(tal[0], o);
+    tal[1] += __shfl_xor(tal[1], o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (tal[0]) atomicAdd(&d.ctl[6], (unsigned long long)tal[0]);  // bcast_sent, bcast_dropped
+    if (tal[1]) atomicAdd(&d.ctl[7], (unsigned long long)tal[1]);
+  }
+}
 
 // MergeMemberList of an external list into row obs at tick p.r - 1 (the last
 // completed round). colq[c] = the listed heartbeat of local member c (< -2:
@@ -461,7 +498,7 @@ void launch_leave(const GhDev& d, int cur, const int32_t* leavers, const int32_t
                   const GhRound& p, hipStream_t s) {
   if (ntl == 0) return;
   scatter(d, leavers, nullptr, nl, 0xFF, s);
-  seg_launch(d, cur, SegSet{nullptr, d.row0, d.nrows, tiles, ntl}, nullptr, p, OpLeave{d, nl, p.shadow_row}, s);
+  seg_launch(d, cur, SegSet{nullptr, d.row0, d.nrows, tiles, ntl}, nullptr, p, OpLeave{d, nl, p.shadow_row, p}, s);
 }
 
 void launch_join_add(const GhDev& d, int cur, const int32_t* joiners, int32_t nj, int32_t introducer,
@@ -472,6 +509,8 @@ void launch_join_add(const GhDev& d, int cur, const int32_t* joiners, int32_t nj
 }
 
 void launch_join_bcast(const GhDev& d, int cur, int32_t introducer, const GhRound& p, hipStream_t s) {
+  if (d.ctl && (d.ctl_kinds & GH_CTL_JOIN))
+    hipLaunchKernelGGL(k_bcast_drop, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, d, introducer, p);
   seg_launch(d, cur, rows_set(d, nullptr, d.row0, d.nrows), d.nd + 4, p, OpJoinBcast{d, cur, introducer, p}, s);
 }
 

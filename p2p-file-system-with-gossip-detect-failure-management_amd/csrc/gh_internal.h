@@ -222,6 +222,10 @@
 #define GH_TAG_PEER 0x50454552u
 #define GH_TAG_PLACE 0x504C4143u
 #define GH_TAG_LINK 0x4C494E4Bu  // 'LINK': the per-message loss draws (gh_link_drop)
+#define GH_TAG_LEAV 0x4C454156u  // 'LEAV', 'JOIN', 'BCST', 'CRMV': the control-message loss draws (gh_ctl_drop,
+#define GH_TAG_JOIN 0x4A4F494Eu  // process_events, k_ctl_recv; SPEC §2 step 6c)
+#define GH_TAG_BCST 0x42435354u
+#define GH_TAG_CRMV 0x43524D56u
 #define GH_MAX_DRAWS (1u << 20)
 
 enum {
@@ -426,6 +430,15 @@ struct GhDev {
   // (gh_part_cut, before gh_link_drop), by LEAVE / JOIN delivery (events.hip)
   // and by k_part_recv (remove.hip)
   int32_t *side;
+  // lossy control messages (gh_set_control_loss; null: none -- the default, loss
+  // off, or kinds == 0): the eight counters of gh_control_loss_stats ([4], [5],
+  // the JOINs, are the host's), then one byte per row [n]: the introducer's
+  // broadcast to that row is lost (gh_ctl_rowdrop; k_bcast_drop writes it,
+  // OpJoinBcast reads it). Non-null only while d.link is set; ctl_kinds = the
+  // GH_CTL_* mask. Read by LEAVE / broadcast delivery (gh_ctl_drop, events.hip)
+  // and by k_ctl_recv (remove.hip)
+  unsigned long long *ctl;
+  int32_t ctl_kinds;
   int32_t *ring;    // ring mode: [world][n][2] (local snapshot count, local position of the sender)
   uint16_t *rcnt;   // ring mode: [ld/tw][n] snapshot-list members per (tile, sender row)
   uint32_t *rbits;  // gathered presence bitmaps of some rows: [world][nr][ncsw]
@@ -973,6 +986,35 @@ __host__ __device__ __forceinline__ unsigned long long* gh_part_counter(const Gh
   return reinterpret_cast<unsigned long long*>(d.side - 2);
 }
 
+// ---- lossy control messages (SPEC §2 step 6c) --------------------------------
+// The control message `sender` -> `receiver` of kind `kind` (one GH_CTL_* bit)
+// of round p.r is lost: block W(tag; a, r, b), word 0 against the sender's out
+// threshold, word 1 against the receiver's in threshold. A pure function of
+// its counter; tal[0] / tal[1] count the message and the dropped one when
+// `count` (the caller runs once per message: a LEAVE is one cell, the
+// broadcast one thread per row in k_bcast_drop). Feature
+// off (d.ctl null): one uniform branch, no Philox.
+__device__ __forceinline__ bool gh_ctl_drop(const GhDev& d, const GhRound& p, int kind, uint32_t tag, uint32_t a,
+                                            uint32_t b, int64_t sender, int64_t receiver, uint32_t* tal, bool count) {
+  if (!d.ctl) return false;
+  if (!(d.ctl_kinds & kind)) return false;
+  const uint32_t* thr = d.link + 4;
+  const uint32_t to = thr[sender], ti = thr[p.n + receiver];
+  bool drop = false;
+  if (to | ti) {  // (two zero thresholds never drop: no draw)
+    uint32_t w[4];
+    gh_philox_block(p.seed, a, (uint32_t)p.r, tag, b, w);
+    drop = gh_link_hit(to, w[0]) || gh_link_hit(ti, w[1]);
+  }
+  if (count) {
+    tal[0]++;
+    tal[1] += drop;
+  }
+  return drop;
+}
+
+__device__ __forceinline__ uint8_t* gh_ctl_rowdrop(const GhDev& d) { return reinterpret_cast<uint8_t*>(d.ctl + 8); }
+
 // ---- launchers (kernels in round.hip / events.hip / place.hip) ----------
 // round.hip
 // Row j receives REMOVE(c) of the REMOVE set of parity dcur (c in that set):
@@ -1028,6 +1070,10 @@ void launch_rm_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s);
 void launch_part_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s);
 void launch_part_recv(const GhDev& d, int dnew, const GhRound& p, hipStream_t s);
 void launch_part_fill(const GhDev& d, int dcur, const GhRound& p, hipStream_t s);
+// gh_set_control_loss with GH_CTL_REMOVE while loss is on: the recipients of
+// D_r per message (k_ctl_recv), in place of launch_part_recv; one_side = the
+// host knows every member is on one side
+void launch_ctl_recv(const GhDev& d, int dnew, const GhRound& p, int one_side, hipStream_t s);
 // base[cur ^ 1] from buffer cur (member c's own heartbeat - GH_BASE_LAG),
 // |D_{r-1}| next to the local counts, empty slow list
 void launch_base(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s);

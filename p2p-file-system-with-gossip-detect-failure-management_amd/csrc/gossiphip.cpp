@@ -151,7 +151,19 @@ struct Engine {
   // allocated then and stay until gh_destroy); host copy of side[] (the
   // joiners the introducer hears, process_events)
   bool part = false;
+  bool one_side = true;  // every member is on one side (k_ctl_recv skips the side test)
   std::vector<int32_t> side_h;
+  // gh_set_control_loss: the mask, whether the call was ever made, the eight
+  // device counters and the broadcast's per-row drop bytes behind them
+  // (8 * 8 + n bytes, allocated by the first call with a kind set; d.ctl points
+  // at them only while loss is on and a kind is set, ctl_refresh), the host's
+  // JOIN counters, and a host copy of gh_set_loss's thresholds (out [n], in
+  // [n]; empty with loss off) for the JOIN draws of process_events
+  int32_t ctl_kinds = 0;
+  bool ctl_called = false;
+  unsigned long long* ctl_buf = nullptr;
+  int64_t ctl_join[2] = {0, 0};
+  std::vector<uint32_t> link_h;
   // gh_census accumulators: one block per column shard (the allgather's
   // slices), one in all for a single engine or row shards
   char* cs_buf = nullptr;
@@ -978,6 +990,25 @@ int process_events(Engine* e, int32_t r) {
     std::vector<int32_t> heard;
     for (int32_t c : joiners)
       if (e->side_h[c] == e->side_h[I]) heard.push_back(c);
+    joiners.swap(heard);
+  }
+  if (e->d.ctl && (e->ctl_kinds & GH_CTL_JOIN) && I >= 0 && I < e->n && e->alive[I]) {
+    // ... and may be lost on its way there (SPEC §2 step 6c): W('JOIN'; c, r,
+    // I) against out[c] and in[I]; the introducer's own restart is local
+    std::vector<int32_t> heard;
+    const uint32_t* thr = e->link_h.data();
+    for (int32_t c : joiners) {
+      if (c != I) {
+        uint32_t w[4];
+        gh_philox_block(p.seed, (uint32_t)c, (uint32_t)r, GH_TAG_JOIN, (uint32_t)I, w);
+        e->ctl_join[0]++;
+        if (gh_link_hit(thr[c], w[0]) || gh_link_hit(thr[(size_t)e->n + I], w[1])) {
+          e->ctl_join[1]++;
+          continue;
+        }
+      }
+      heard.push_back(c);
+    }
     joiners.swap(heard);
   }
   if (!joiners.empty() && I >= 0 && I < e->n && e->alive[I]) {
@@ -2231,7 +2262,12 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     if (e->part) launch_part_cols(e->d, e->cur, e->dcur, p, e->stream);
     launch_finish(e->d, e->dcur, p, e->stream);
     if (e->rm_ref) launch_rm_recv(e->d, e->dcur ^ 1, p, e->stream);
-    if (e->part) launch_part_recv(e->d, e->dcur ^ 1, p, e->stream);
+    if (e->part) {
+      if (e->d.ctl && (e->ctl_kinds & GH_CTL_REMOVE))  // lossy REMOVEs: per message (SPEC §2 step 6c)
+        launch_ctl_recv(e->d, e->dcur ^ 1, p, e->one_side, e->stream);
+      else
+        launch_part_recv(e->d, e->dcur ^ 1, p, e->stream);
+    }
     HIPCHK(e, hipGetLastError());
     e->cur ^= 1;
     e->dcur ^= 1;
@@ -2834,6 +2870,21 @@ int gh_journal_rounds(void* h, gh_journal_round* out, int64_t cap, int64_t* n_to
   return GH_OK;
 }
 
+// Lossy control messages (gh_set_control_loss): d.ctl points at the counters
+// only while loss is on and a kind is set, so that every kernel's test is one
+// null pointer; zero = the counters start again (every gh_set_control_loss and
+// gh_set_loss).
+static int ctl_refresh(Engine* e, bool zero) {
+  GhDev& d = e->d;
+  d.ctl = d.link && e->ctl_kinds ? e->ctl_buf : nullptr;
+  d.ctl_kinds = e->ctl_kinds;
+  if (zero) {
+    e->ctl_join[0] = e->ctl_join[1] = 0;
+    if (e->ctl_buf) HIPCHK(e, hipMemsetAsync(e->ctl_buf, 0, 8 * sizeof(unsigned long long), e->stream));
+  }
+  return GH_OK;
+}
+
 // Lossy links (SPEC §2 step 6a; gh_internal.h GhDev.link, gh_link_drop): the
 // thresholds live on the device only, replicated on every shard, so setting
 // them needs no exchange; the counters are summed over the shards on read
@@ -2847,11 +2898,16 @@ int gh_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32) {
   if (!out_q32 && !in_q32) {
     dfree(e, d.link);
     d.link = nullptr;
-    return GH_OK;
+    e->link_h.clear();
+    return ctl_refresh(e, true);
   }
   const size_t n = (size_t)e->n;
   int rc;
   if (!d.link && (rc = dalloc(e, &d.link, 4 + 2 * n, 0))) return rc;
+  e->link_h.assign(2 * n, 0u);
+  if (out_q32) std::copy(out_q32, out_q32 + n, e->link_h.begin());
+  if (in_q32) std::copy(in_q32, in_q32 + n, e->link_h.begin() + n);
+  if ((rc = ctl_refresh(e, true))) return rc;
   HIPCHK(e, hipMemsetAsync(d.link, 0, sizeof(uint32_t) * (4 + 2 * n), e->stream));
   if (out_q32) HIPCHK(e, hipMemcpyAsync(d.link + 4, out_q32, sizeof(uint32_t) * n, hipMemcpyHostToDevice, e->stream));
   if (in_q32) HIPCHK(e, hipMemcpyAsync(d.link + 4 + n, in_q32, sizeof(uint32_t) * n, hipMemcpyHostToDevice, e->stream));
@@ -2882,6 +2938,38 @@ int gh_get_loss(void* h, int32_t* enabled, uint32_t* out_q32, uint32_t* in_q32) 
 // with its counter and the recipient bitmaps, switches REMOVE delivery to
 // bitmap recipients (d.rlist) and, when a REMOVE set is pending, fills its
 // recipients by rule D4, so the round that delivers it is unchanged.
+// Arms a never-armed engine (the caller synchronised the stream): the
+// allocations, every member on side 0, cut = 0, and the pending REMOVE set's
+// recipients by rule D4.
+static int part_arm(Engine* e) {
+  const size_t n = (size_t)e->n;
+  GhDev& d = e->d;
+  int rc;
+  GhDev nd = d;  // armed only when every allocation succeeded
+  int32_t* buf = nullptr;
+  nd.nw = ((int64_t)e->n + 31) / 32;
+  const size_t words = (size_t)e->ld * nd.nw;
+  if ((rc = dalloc(e, &buf, n + 2, 0)) || (rc = dalloc(e, &nd.rcv[0], words, 0)) ||
+      (rc = dalloc(e, &nd.rcv[1], words, 0)) || (rc = dalloc(e, &nd.cdet, words, 0)) ||
+      (rc = dalloc(e, &nd.ccnt, 2 * (size_t)e->ld + 2, 0))) {
+    dfree(e, buf);
+    dfree(e, nd.rcv[0]);
+    dfree(e, nd.rcv[1]);
+    dfree(e, nd.cdet);
+    return rc;
+  }
+  nd.side = buf + 2;
+  nd.rlist = 1;
+  d = nd;
+  e->part = true;
+  e->side_h.assign(n, 0);
+  // the pending REMOVE set (parity dcur) was detected with no sides
+  launch_part_fill(d, e->dcur, round_params(e, e->round + 1), e->stream);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemsetAsync(d.side - 2, 0, sizeof(int32_t) * (n + 2), e->stream));  // cut = 0, every side 0
+  return GH_OK;
+}
+
 int gh_set_partition(void* h, const int32_t* side) {
   Engine* e = static_cast<Engine*>(h);
   if (!e) return GH_EINVAL;
@@ -2896,29 +2984,7 @@ int gh_set_partition(void* h, const int32_t* side) {
   if ((rc = check_lost(e))) return rc;
   HIPCHK(e, hipStreamSynchronize(e->stream));
   GhDev& d = e->d;
-  if (!e->part) {
-    GhDev nd = d;  // armed only when every allocation succeeded
-    int32_t* buf = nullptr;
-    nd.nw = ((int64_t)e->n + 31) / 32;
-    const size_t words = (size_t)e->ld * nd.nw;
-    if ((rc = dalloc(e, &buf, n + 2, 0)) || (rc = dalloc(e, &nd.rcv[0], words, 0)) ||
-        (rc = dalloc(e, &nd.rcv[1], words, 0)) || (rc = dalloc(e, &nd.cdet, words, 0)) ||
-        (rc = dalloc(e, &nd.ccnt, 2 * (size_t)e->ld + 2, 0))) {
-      dfree(e, buf);
-      dfree(e, nd.rcv[0]);
-      dfree(e, nd.rcv[1]);
-      dfree(e, nd.cdet);
-      return rc;
-    }
-    nd.side = buf + 2;
-    nd.rlist = 1;
-    d = nd;
-    e->part = true;
-    e->side_h.assign(n, 0);
-    // the pending REMOVE set (parity dcur) was detected with no sides
-    launch_part_fill(d, e->dcur, round_params(e, e->round + 1), e->stream);
-    HIPCHK(e, hipGetLastError());
-  }
+  if (!e->part && (rc = part_arm(e))) return rc;
   HIPCHK(e, hipMemsetAsync(d.side - 2, 0, sizeof(int32_t) * (n + 2), e->stream));  // cut = 0, every side 0
   if (side) {
     HIPCHK(e, hipMemcpyAsync(d.side, side, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
@@ -2926,6 +2992,7 @@ int gh_set_partition(void* h, const int32_t* side) {
   } else {
     e->side_h.assign(n, 0);
   }
+  e->one_side = std::all_of(e->side_h.begin(), e->side_h.end(), [&](int32_t x) { return x == e->side_h[0]; });
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return GH_OK;
 }
@@ -2952,6 +3019,49 @@ int gh_partition_stats(void* h, int64_t* cut) {
   HIPCHK(e, hipMemcpyAsync(&v, gh_part_counter(e->d), sizeof v, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   if (cut) *cut = v;
+  return GH_OK;
+}
+
+int gh_set_control_loss(void* h, int32_t kinds) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (e->world > 1) return set_err(e, GH_EINVAL, "gh_set_control_loss: sharded handles are not supported");
+  if (e->rm_ref) return set_err(e, GH_EINVAL, "gh_set_control_loss: GH_REMOVE_LIST engines are not supported");
+  if (kinds < 0 || kinds > (GH_CTL_REMOVE | GH_CTL_LEAVE | GH_CTL_JOIN))
+    return set_err(e, GH_EINVAL, "gh_set_control_loss: kinds outside 0..7");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (kinds && !e->ctl_buf && (rc = dalloc(e, &e->ctl_buf, 8 + ((size_t)e->n + 7) / 8, 0))) return rc;
+  if ((kinds & GH_CTL_REMOVE) && !e->part && (rc = part_arm(e))) return rc;
+  e->ctl_kinds = kinds;
+  e->ctl_called = true;
+  if ((rc = ctl_refresh(e, true))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_get_control_loss(void* h, int32_t* kinds) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (kinds) *kinds = e->ctl_kinds;
+  return GH_OK;
+}
+
+int gh_control_loss_stats(void* h, int64_t* out8) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  if (!e->ctl_called) return set_err(e, GH_EINVAL, "gh_set_control_loss was never called");
+  int64_t v[8] = {};
+  if (e->ctl_buf) {
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipMemcpyAsync(v, e->ctl_buf, sizeof v, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  }
+  v[4] = e->ctl_join[0];
+  v[5] = e->ctl_join[1];
+  if (out8) std::copy(v, v + 8, out8);
   return GH_OK;
 }
 

@@ -264,7 +264,123 @@ __global__ __launch_bounds__(256) void k_part_fill(GhDev d, int dcur, GhRound p)
   }
 }
 
+// ---- lossy control messages (gh_set_control_loss, GH_CTL_REMOVE; SPEC §2
+// step 6c) --------------------------------------------------------------------
+// REMOVE(c) of D_r is one message per (detector i, row j), i != j and reach(i,
+// j), dropped by Philox(K; i, j, 'CRMV', 0) under the key K = words 0, 1 of
+// W('CRMV'; c, r, 0) against out[i] and in[j]; row j receives it iff one of
+// them arrives. One workgroup per member c of D_r (grid-stride): K once per
+// workgroup, the nonzero words of det(c) listed in LDS as in k_rm_recv (past
+// the cap: the full scan of det(c)), then a thread per 32 receivers, each
+// walking the detectors until the first message that arrives: at rate p an
+// expected 1 / (1 - p^2) draws per pair. The words are walked in the order
+// they were listed, which is not ascending and varies from run to run; only
+// the number of draws depends on it, every message's fate being a pure
+// function of its counter. in[j] == always settles a receiver
+// and out[i] == always skips a detector without a draw, and so do two zero
+// thresholds. SIDES = false: the host knows every member is on one side.
+// Counters (ctl[0] pairs with a message and j alive, ctl[1] those with every
+// message dropped): reduced per workgroup, one atomic each. Rows at or past n
+// get no bit; the thresholds and side[] are read below n only.
+struct CtlWalk {
+  uint64_t key;
+  const uint32_t* out;
+  uint32_t tin;
+  int64_t j;
+  bool has, got;
+  // the detectors of word w (bits v): true when the walk is over
+  template <bool SIDES>
+  __device__ __forceinline__ bool word(const int32_t* sd, int64_t w, uint32_t v, int32_t n) {
+    for (; v; v &= v - 1u) {
+      const int64_t i = 32 * w + __builtin_ctz(v);
+      if (i >= n) break;
+      if (i == j) continue;  // Remove skips self (:344-346)
+      if (SIDES && sd[i] != sd[j]) continue;
+      has = true;
+      if (tin == GH_LOSS_ALWAYS) return true;
+      const uint32_t to = out[i];
+      if (to == GH_LOSS_ALWAYS) continue;
+      if ((to | tin) == 0u) return got = true;
+      uint32_t b[4];
+      gh_philox_block(key, (uint32_t)i, (uint32_t)j, GH_TAG_CRMV, 0u, b);
+      if (!(b[0] < to || b[1] < tin)) return got = true;
+    }
+    return false;
+  }
+};
+
+template <bool SIDES>
+__global__ __launch_bounds__(256) void k_ctl_recv(GhDev d, int dnew, GhRound p) {
+  __shared__ uint32_t s_w[RM_NZ_CAP], s_v[RM_NZ_CAP];
+  __shared__ int s_nz, s_tot[2];
+  const int nd = d.nd[2 + dnew];
+  const uint32_t* thr = d.link + 4;
+  if (threadIdx.x < 2) s_tot[threadIdx.x] = 0;
+  int pairs = 0, missed = 0;
+  for (int q = blockIdx.x; q < nd; q += gridDim.x) {
+    const int64_t c = d.dlist[(int64_t)dnew * p.ld + q];
+    if (c < 0 || c >= d.ncol) continue;  // (a padded column is never detected; uniform)
+    uint32_t kw[4];
+    gh_philox_block(p.seed, (uint32_t)c, (uint32_t)p.r, GH_TAG_CRMV, 0u, kw);
+    const uint32_t* dcol = d.cdet + c * d.nw;
+    if (threadIdx.x == 0) s_nz = 0;
+    __syncthreads();
+    for (int64_t w = threadIdx.x; w < d.nw; w += 256) {
+      const uint32_t v = dcol[w];
+      if (v) {
+        const int at = atomicAdd(&s_nz, 1);
+        if (at < RM_NZ_CAP) {
+          s_w[at] = (uint32_t)w;
+          s_v[at] = v;
+        }
+      }
+    }
+    __syncthreads();
+    const int nz = s_nz;
+    for (int64_t w = threadIdx.x; w < d.nw; w += 256) {
+      uint32_t out = 0;
+      for (int b = 0; b < 32; ++b) {
+        const int64_t j = 32 * w + b;
+        if (j >= p.n) break;
+        CtlWalk k{(uint64_t)kw[0] | ((uint64_t)kw[1] << 32), thr, thr[p.n + j], j, false, false};
+        if (nz <= RM_NZ_CAP) {
+          for (int e = 0; e < nz; ++e)
+            if (k.word<SIDES>(d.side, s_w[e], s_v[e], p.n)) break;
+        } else {
+          for (int64_t x = 0; x < d.nw; ++x)
+            if (k.word<SIDES>(d.side, x, dcol[x], p.n)) break;
+        }
+        out |= (uint32_t)k.got << b;
+        const bool cnt = k.has && d.alive[j];
+        pairs += cnt;
+        missed += cnt && !k.got;
+      }
+      d.rcv[dnew][c * d.nw + w] = out;
+    }
+    __syncthreads();  // s_nz / the list before the next member
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    pairs += __shfl_xor(pairs, o);
+    missed += __shfl_xor(missed, o);
+  }
+  __syncthreads();  // (s_tot zeroed; every thread reaches this)
+  if ((threadIdx.x & 63) == 0 && pairs) {
+    atomicAdd(&s_tot[0], pairs);
+    if (missed) atomicAdd(&s_tot[1], missed);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_tot[threadIdx.x]) atomicAdd(&d.ctl[threadIdx.x], (unsigned long long)s_tot[threadIdx.x]);
+}
+
 }  // namespace
+
+void launch_ctl_recv(const GhDev& d, int dnew, const GhRound& p, int one_side, hipStream_t s) {
+  const dim3 grid((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, p.n)));
+  if (one_side)
+    hipLaunchKernelGGL(k_ctl_recv<false>, grid, dim3(256), 0, s, d, dnew, p);
+  else
+    hipLaunchKernelGGL(k_ctl_recv<true>, grid, dim3(256), 0, s, d, dnew, p);
+}
 
 void launch_part_cols(const GhDev& d, int cur, int dcur, const GhRound& p, hipStream_t s) {
   (void)hipMemsetAsync(d.ccnt, 0, sizeof(int32_t) * (2 * p.ld + 2), s);

@@ -32,11 +32,16 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_EPLACEMENT_STARVED, GH_EV_CRASH, GH_EV_JOIN, GH_EV_LEAVE, GH_OK, GH_PEER_PULL,
                    GH_PEER_RING, Config, PlanEntry,
                    GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS,
-                   GH_LOSS_ALWAYS, GH_LOSS_NEVER, GH_PART_SIDES)
+                   GH_LOSS_ALWAYS, GH_LOSS_NEVER, GH_PART_SIDES, GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN)
 
 __all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "Journal", "GossipError", "default_config",
            "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
-           "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS", "GH_PART_SIDES"]
+           "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS", "GH_PART_SIDES", "GH_CTL_REMOVE", "GH_CTL_LEAVE", "GH_CTL_JOIN",
+           "CONTROL_LOSS_STATS"]
+
+# gh_control_loss_stats, in ABI order
+CONTROL_LOSS_STATS = ("remove_pairs", "remove_missed", "leave_sent", "leave_dropped", "join_sent", "join_dropped",
+                      "bcast_sent", "bcast_dropped")
 
 # gh_journal_read, in ABI order: per member id [N] (detectors int64, the rest int32), then the three histograms
 # int64 [GH_JOURNAL_BINS]
@@ -423,8 +428,10 @@ class Engine:
         on its way out or inbound[g] on its way in (slave/slave.go:527-542 sends
         its lists as UDP datagrams). Each side is a float in [0, 1], [N]
         floats, or raw uint32 [N] thresholds in units of 2^-32 (0xFFFFFFFF:
-        always); None = never. Both None switch loss off. JOIN, LEAVE, REMOVE
-        and merge_list stay reliable. Every call zeroes loss_stats()."""
+        always); None = never. Both None switch loss off. JOIN, LEAVE and
+        REMOVE cross the same links only where set_control_loss opts them in;
+        merge_list stays reliable. Every call zeroes loss_stats() and
+        control_loss_stats()."""
         o, i = self._loss_q32(out), self._loss_q32(inbound)
         self._chk(self.lib.gh_set_loss(self.h, None if o is None else _p(o), None if i is None else _p(i)))
 
@@ -476,6 +483,34 @@ class Engine:
         cut = C.c_int64()
         self._chk(self.lib.gh_partition_stats(self.h, C.byref(cut)))
         return cut.value
+
+    def set_control_loss(self, kinds):
+        """Which control messages cross the lossy links of set_loss
+        (gh_set_control_loss): a mask of GH_CTL_REMOVE, GH_CTL_LEAVE and
+        GH_CTL_JOIN (the JOIN to the introducer and its broadcast); 0, the
+        default, is none. It acts only while set_loss is on, from the next
+        round on. With GH_CTL_REMOVE it arms the engine as set_partition(None)
+        does. Every call zeroes control_loss_stats(). GossipError(GH_EINVAL)
+        for a mask outside 0..7, on a sharded engine and on a GH_REMOVE_LIST
+        engine."""
+        k = int(kinds)
+        self._chk(self.lib.gh_set_control_loss(self.h, k if -2 ** 31 <= k < 2 ** 31 else -1))
+
+    def control_loss(self):
+        """The mask of set_control_loss (gh_get_control_loss)."""
+        k = C.c_int32()
+        self._chk(self.lib.gh_get_control_loss(self.h, C.byref(k)))
+        return k.value
+
+    def control_loss_stats(self):
+        """The counters since the last set_control_loss or set_loss as a dict
+        (CONTROL_LOSS_STATS; gh_control_loss_stats): REMOVE counts (row,
+        member) pairs with a message and those that missed every one of them,
+        the others messages sent and dropped. GossipError(GH_EINVAL) before the
+        first set_control_loss."""
+        v = (C.c_int64 * 8)()
+        self._chk(self.lib.gh_control_loss_stats(self.h, v))
+        return dict(zip(CONTROL_LOSS_STATS, (int(x) for x in v)))
 
     def merge_list(self, observer, ids, hb):
         """MergeMemberList (slave/slave.go:414-440) of a received list into
@@ -780,7 +815,8 @@ class Cluster:
 
     def set_loss(self, out=None, inbound=None):
         """Per-member drop rates of the gossip datagrams from the next tick
-        on (Engine.set_loss); JOIN, LEAVE and REMOVE stay reliable."""
+        on (Engine.set_loss); JOIN, LEAVE and REMOVE stay reliable unless
+        set_control_loss opts them in."""
         self.engine.set_loss(out, inbound)
 
     def loss_stats(self):
@@ -795,6 +831,20 @@ class Cluster:
         if self.elect:
             raise ValueError("partitions are not modelled with elect=True")
         self.engine.set_partition(side)
+
+    def set_control_loss(self, kinds):
+        """Which control messages cross the lossy links from the next tick on
+        (Engine.set_control_loss). With elect=True: ValueError (the election's
+        RPCs over lossy links are not modelled)."""
+        if self.elect:
+            raise ValueError("lossy control messages are not modelled with elect=True")
+        self.engine.set_control_loss(kinds)
+
+    def control_loss_stats(self):
+        """The control-message counters (Engine.control_loss_stats)."""
+        if self.elect:
+            raise ValueError("lossy control messages are not modelled with elect=True")
+        return self.engine.control_loss_stats()
 
     def partition_stats(self):
         """Gossip messages cut since set_partition (Engine.partition_stats)."""

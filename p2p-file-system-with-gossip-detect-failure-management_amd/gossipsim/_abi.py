@@ -39,6 +39,7 @@ GH_JOURNAL_OFF, GH_JOURNAL_DETECT, GH_JOURNAL_VIEWS = 0, 1, 3
 GH_JOURNAL_BINS = 64
 GH_LOSS_NEVER, GH_LOSS_ALWAYS = 0, 0xFFFFFFFF
 GH_PART_SIDES = 64
+GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN = 1, 2, 4
 # gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
 # environment variable GH_<NAME> that gh_create reads)
 KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
@@ -110,6 +111,9 @@ SYMBOLS = [
     ("gh_set_partition", C.c_int, [_vp, _vp]),
     ("gh_get_partition", C.c_int, [_vp, _P(_i32), _vp]),
     ("gh_partition_stats", C.c_int, [_vp, _P(_i64)]),
+    ("gh_set_control_loss", C.c_int, [_vp, _i32]),
+    ("gh_get_control_loss", C.c_int, [_vp, _P(_i32)]),
+    ("gh_control_loss_stats", C.c_int, [_vp, _P(_i64)]),
     ("gh_merge_list", C.c_int, [_vp, _i32, _vp, _vp, _i64, _P(_i64)]),
     ("gh_put", C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     ("gh_put_conflicts", C.c_int, [_vp, _vp, _i64, _i32, _vp]),
