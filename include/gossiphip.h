@@ -219,6 +219,53 @@ int gh_lsm(void* h, int32_t observer, int32_t* ids, int32_t* hb, int32_t* ts,
 int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min,
               int32_t* hb_max, int64_t* hb_sum, int32_t* age_max, int64_t* age_hist);
 
+/* Membership groups and view digests: which clusters the running members'
+ * lists now form, and which running members hold the same view, computed on
+ * the device by read-only passes over the table (no reference counterpart;
+ * the nearest is comparing the `lsm` of every VM, slave/slave.go:558-561).
+ * Defined on what gh_export_state would return now (hb, alive; as for
+ * gh_census, queued events and the D7 shadow entries are not in it).
+ *   Edges: E = {(i, c) : i != c, alive[i], alive[c], hb[i][c] >= 0}, "running
+ *   i lists running c". A stopped member has no edges: nothing bridges through
+ *   a stopped member two groups both still list, nor through a stopped row's
+ *   stale list. Tombstones and absent cells are no edge.
+ *   group[m], m running = the lowest member id of m's weakly connected
+ *   component of (running members, E), direction ignored; m stopped: -1. A
+ *   running member nobody lists and that lists nobody is its own group. Weak,
+ *   because one listing in either direction lets gossip -- and with it the
+ *   missing entries -- flow (a pull from a peer that lists the receiver, a
+ *   ring target taken from the sender's list): two different groups never
+ *   hear from each other again except through a JOIN, which is the "never
+ *   re-merge" statement of gh_set_partition below.
+ *   view_digest[i], i running = the sum modulo 2^64 of mix(c) over every c
+ *   with hb[i][c] >= 0, the row's own entry and the stopped members it still
+ *   lists included; i stopped: 0. mix(c), in uint64:
+ *     z = (c + 1) * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31.
+ *   Equal views give equal digests, so the distinct digests among the running
+ *   rows count the distinct views; two different views collide with
+ *   probability about 2^-64.
+ *   *n_groups = the running m with group[m] == m. *passes = the hooking
+ *   passes the call ran (>= 1; diagnostic, it may differ between engines that
+ *   hold the same state).
+ * group, view_digest: [N] by member id. Any output may be NULL, both arrays
+ * included (the counts are still returned; without view_digest no digest is
+ * computed). A NULL handle returns GH_EINVAL before any device is touched.
+ * Read-only: the table, the round, the statistics, the draw counters and
+ * every diagnostic are unchanged. Each pass reads the table once (what a
+ * gh_census reads); labels are member ids that only decrease, so the passes
+ * end: two on a healthy cluster, two or three on the split and shattered
+ * states measured in DESIGN.md "Groups". Nothing is allocated or launched before the first call
+ * (gh_footprint, gh_memory_info at creation and gh_step's launches do not
+ * change); the first call allocates 20 N + 16 bytes of scratch per shard,
+ * kept until gh_destroy. Any engine: both peer modes, detection modes, list
+ * orders and remove modes, armed or not, loss and journal on or off.
+ * Additive under ABI 7. On a sharded handle (either layout) the call is
+ * collective: every rank calls it with the same outputs NULL and gets the
+ * global result. */
+int gh_groups(void* h, int32_t* group, uint64_t* view_digest, int64_t* n_groups,
+              int32_t* passes);
+
 /* Detection journal: what a failure detector is judged by -- how long a crash
  * takes to be detected, how often a running member is declared dead, how long
  * the verdict takes to reach every view -- kept on the device and updated once

@@ -1200,6 +1200,24 @@ struct GhCensus {
   unsigned long long *hist; // [GH_CENSUS_BINS] present cells by min(age, GH_CENSUS_BINS - 1)
 };
 void launch_census(const GhDev& d, int cur, int32_t r, const GhCensus& o, hipStream_t s);
+// groups.hip (gh_groups): connected groups of the running members and per-row
+// view digests, read-only passes over buffer cur (for round r). All arrays are
+// [n] by member id and replicated on every shard. One pass: launch_groups_walk
+// adds this engine's owned rows and local columns into rmax / cmax (0 on
+// entry; minima as INT32_MAX - label, so they reduce across shards with MAX)
+// and, when first, into digest (0 on entry; SUM); launch_groups_hook_m, then
+// launch_groups_hook on the reduced arrays hook and compress the labels,
+// clear rmax / cmax and set flag[0] when a label moved.
+struct GhGroups {
+  int32_t *label;              // running: a member of its group, at most its own id; stopped: -1
+  int32_t *rmax, *cmax;        // per row / column: INT32_MAX - (lowest label across its edges), 0 none
+  unsigned long long *digest;  // per row: sum of mix(c) over its listed members
+  int32_t *flag;               // [0] a label moved in this pass
+};
+void launch_groups_init(const GhDev& d, const GhGroups& o, hipStream_t s);
+void launch_groups_walk(const GhDev& d, int cur, int32_t r, const GhGroups& o, int first, hipStream_t s);
+void launch_groups_hook_m(const GhDev& d, const GhGroups& o, hipStream_t s);
+void launch_groups_hook(const GhDev& d, const GhGroups& o, hipStream_t s);
 // files.hip (gh_file_audit / gh_file_select): read-only passes over this
 // shard's file slots. abits / mbits: the availability set and the master's
 // list as flat bitmaps over the member ids ((n + 31) / 32 words), written by

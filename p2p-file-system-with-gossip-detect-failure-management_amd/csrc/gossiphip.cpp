@@ -168,6 +168,9 @@ struct Engine {
   // slices), one in all for a single engine or row shards
   char* cs_buf = nullptr;
   size_t cs_bytes = 0;
+  // gh_groups scratch, allocated by the first call and kept: digests u64 [n],
+  // then labels, row and column minima int32 [n] each, then 4 flag words
+  char* gr_buf = nullptr;
   // gh_file_audit / gh_file_select scratch (counters, load / sole, the two
   // member bitmaps, the selected ids), grown on demand, never shrunk
   char* fa_buf = nullptr;
@@ -2754,6 +2757,58 @@ int gh_census(void* h, int32_t* listed, int32_t* tombstoned, int32_t* hb_min, in
     if (age_max && nc > 0) std::memcpy(age_max + c0, w + 4 * ncs, sizeof(int32_t) * nc);
     for (int64_t c = 0; hb_min && c < nc; ++c) hb_min[c0 + c] = w[2 * ncs + c] < 0 ? -1 : INT32_MAX - w[2 * ncs + c];
   }
+  return GH_OK;
+}
+
+// Connected groups of the running members and per-row view digests
+// (groups.hip). Labels, minima and digests are [N] by member id on every
+// shard: a shard walks its own rows and columns, the minima are reduced with
+// MAX (as INT32_MAX - x) and the digests with SUM, and every shard runs the
+// same O(N) hook and jump on the same arrays, so all see the same `changed`.
+int gh_groups(void* h, int32_t* group, uint64_t* view_digest, int64_t* n_groups, int32_t* passes) {
+  Engine* e = static_cast<Engine*>(h);
+  if (!e) return GH_EINVAL;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  int rc;
+  if ((rc = check_lost(e))) return rc;
+  const GhDev& d = e->d;
+  const size_t n = (size_t)e->n;
+  if (!e->gr_buf && (rc = dalloc(e, &e->gr_buf, 20 * n + 16, 0))) return rc;
+  GhGroups o;
+  o.digest = reinterpret_cast<unsigned long long*>(e->gr_buf);
+  o.label = reinterpret_cast<int32_t*>(e->gr_buf + 8 * n);
+  o.rmax = o.label + n;
+  o.cmax = o.rmax + n;
+  o.flag = o.cmax + n;
+  HIPCHK(e, hipMemsetAsync(o.digest, 0, 8 * n, e->stream));
+  HIPCHK(e, hipMemsetAsync(o.rmax, 0, 8 * n + 16, e->stream));
+  launch_groups_init(d, o, e->stream);
+  int32_t np = 0;
+  for (int32_t changed = 1; changed; ++np) {
+    const bool first = np == 0 && view_digest != nullptr;
+    launch_groups_walk(d, e->cur, e->round + 1, o, first, e->stream);  // (the current buffer is for the round about to run)
+    HIPCHK(e, hipGetLastError());
+    if (e->world > 1) {
+      COMMCHK(e, e->comm->allreduce(o.rmax, o.rmax, 2 * n, GH_DT_I32, GH_OP_MAX, e->stream));
+      if (first) COMMCHK(e, e->comm->allreduce(o.digest, o.digest, n, GH_DT_U64, GH_OP_SUM, e->stream));
+    }
+    launch_groups_hook_m(d, o, e->stream);
+    launch_groups_hook(d, o, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(&changed, o.flag, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemsetAsync(o.flag, 0, sizeof(int32_t), e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  }
+  std::vector<int32_t> lab(n);
+  HIPCHK(e, hipMemcpyAsync(lab.data(), o.label, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+  if (view_digest)
+    HIPCHK(e, hipMemcpyAsync(view_digest, o.digest, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  int64_t ng = 0;
+  for (size_t m = 0; m < n; ++m) ng += lab[m] == (int32_t)m;
+  if (group) std::memcpy(group, lab.data(), sizeof(int32_t) * n);
+  if (n_groups) *n_groups = ng;
+  if (passes) *passes = np;
   return GH_OK;
 }
 

@@ -34,7 +34,7 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS,
                    GH_LOSS_ALWAYS, GH_LOSS_NEVER, GH_PART_SIDES, GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN)
 
-__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "FileAudit", "Journal", "GossipError", "default_config",
+__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "Groups", "FileAudit", "Journal", "GossipError", "default_config",
            "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
            "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS", "GH_PART_SIDES", "GH_CTL_REMOVE", "GH_CTL_LEAVE", "GH_CTL_JOIN",
            "CONTROL_LOSS_STATS"]
@@ -56,6 +56,24 @@ JOURNAL_ROUND_DTYPE = np.dtype([("round", np.int32), ("running", np.int32), ("fa
 
 # gh_census: per member id [N] (age_hist: [GH_CENSUS_BINS] over every listed cell)
 Census = namedtuple("Census", "listed tombstoned hb_min hb_max hb_sum age_max age_hist")
+
+
+class Groups(namedtuple("Groups", "group digest n_groups passes")):
+    """gh_groups: group int32 [N] and digest uint64 [N] by member id, the
+    number of groups and the passes the call ran (diagnostic)."""
+    __slots__ = ()
+
+    def sizes(self):
+        """{root: members of its group}."""
+        roots, cnt = np.unique(self.group[self.group >= 0], return_counts=True)
+        return dict(zip(roots.tolist(), cnt.tolist()))
+
+    @property
+    def n_views(self):
+        """Distinct views (digests) among the running rows."""
+        return int(np.unique(self.digest[self.group >= 0]).size)
+
+
 # gh_file_audit: files, starved ints; working_hist int64 [GH_AUDIT_BINS]; load, sole int32 [N] by member id
 FileAudit = namedtuple("FileAudit", "files working_hist starved load sole")
 
@@ -364,6 +382,20 @@ class Engine:
                      np.empty(n, np.int64), np.empty(n, np.int32), np.empty(_abi.GH_CENSUS_BINS, np.int64))
         self._chk(self.lib.gh_census(self.h, *[_p(a) for a in out]))
         return out
+
+    def groups(self):
+        """Groups(group, digest, n_groups, passes) of the current table,
+        computed on the device (gh_groups): group[m] = the lowest member id of
+        running m's weakly connected component of "running i lists running c"
+        (-1 for a stopped m), digest[i] = the 64-bit digest of the set of
+        members running row i lists (0 for a stopped row; equal views, equal
+        digests), n_groups, and the passes over the table the call took.
+        Defined on what export_state would return now; read-only."""
+        n = self.n
+        group, digest = np.empty(n, np.int32), np.empty(n, np.uint64)
+        ng, np_ = C.c_int64(), C.c_int32()
+        self._chk(self.lib.gh_groups(self.h, _p(group), _p(digest), C.byref(ng), C.byref(np_)))
+        return Groups(group, digest, ng.value, np_.value)
 
     def journal_enable(self, mode=GH_JOURNAL_DETECT, log_rounds=0):
         """Start (or, with GH_JOURNAL_OFF, drop) the detection journal
@@ -688,6 +720,11 @@ class ShardGroup:
             return res[0]
         return call
 
+    def groups(self):
+        """Engine.groups() as the collective call it is on shards: every rank
+        runs it, all must agree, rank 0's Groups is returned."""
+        return self.__getattr__("groups")()
+
     @property
     def round(self):
         return self.engines[0].round
@@ -798,6 +835,13 @@ class Cluster:
         """Every member's view count, heartbeat spread and age distribution
         over the running members (Engine.census)."""
         return self.engine.census()
+
+    def groups(self):
+        """The clusters the running members' lists now form (Engine.groups),
+        as sorted member-id arrays, largest first (ties: lowest root first)."""
+        g = self.engine.groups().group
+        out = [np.flatnonzero(g == r) for r in np.unique(g[g >= 0])]
+        return sorted(out, key=lambda a: (-a.size, int(a[0])))
 
     def journal_enable(self, mode=GH_JOURNAL_DETECT, log_rounds=0):
         """Journal every tick from now on (Engine.journal_enable). Crashes an

@@ -102,6 +102,7 @@ SYMBOLS = [
     ("gh_read_detectors", C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     ("gh_lsm", C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _P(_i64)]),
     ("gh_census", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gh_groups", C.c_int, [_vp, _vp, _vp, _P(_i64), _P(_i32)]),
     ("gh_journal_enable", C.c_int, [_vp, _i32, _i64]),
     ("gh_journal_read", C.c_int, [_vp] + [_vp] * 14),
     ("gh_journal_rounds", C.c_int, [_vp, _P(JournalRound), _i64, _P(_i64), _P(_i64)]),
