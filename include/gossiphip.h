@@ -757,6 +757,110 @@ int gh_read_timing(void* h, double* total_ms, int64_t* launches);
 /* Block until all queued device work has finished. */
 int gh_sync(void* h);
 
+/* Cluster ensembles (SPEC.md §11): B independent clusters of the same N
+ * (2..GH_ENS_MAX_MEMBERS) and fanout behind one handle, each with its own
+ * seed, T_fail, T_cleanup, per-member loss thresholds and round counter, all
+ * advanced by one launch per gh_ens_step call: one workgroup owns one cluster
+ * and runs every round of the call out of registers and LDS (DESIGN.md
+ * "Ensemble"). For sweeps over seeds x loss rates x timeouts of small
+ * clusters, where an engine's round is launch overhead. No reference
+ * counterpart: the nearest is running the reference cluster (main.go:27-33,
+ * about ten processes) B times.
+ * Every cluster advances by SPEC §2 restricted to: pull mode, canonical
+ * detection, GH_ORDER_ID, GH_REMOVE_ALL (D4), GH_EV_CRASH events, the lossy
+ * links of step 6a. Cluster b is bit for bit what a gh_create engine with
+ * params[b]'s seed and timeouts, the same N, fanout and min_members, the same
+ * crashes and gh_set_loss(out[b], in[b]) computes: tables, alive, every
+ * gh_round_stats field, the failed set, sent / dropped.
+ * Not supported (use an engine): ring mode, quirk detection, append order,
+ * GH_REMOVE_LIST, joins and leaves, partitions, lossy control messages, files,
+ * election, shards, N > 128.
+ *   State: per cluster SPEC §1's tables, alive and round, plus the pending
+ *   REMOVE set D_{r-1} (per member the rows that detected it and the lowest
+ *   of them). It persists between gh_ens_step calls: R calls of one round
+ *   equal one call of R rounds. gh_ens_create leaves every cluster empty (no
+ *   cell, nobody running, round 0). gh_ens_init_full: every cluster, every
+ *   row alive holding every member at (hb0, ts0) (hb0 < 0: GH_ERANGE).
+ *   gh_ens_import_state: one cluster's hb [N][N], ts [N][N], alive [N] as
+ *   gh_import_state takes them (hb < -2: GH_ERANGE, nothing imported). Both
+ *   set the round counter (>= 0) and clear the cluster's pending REMOVE set
+ *   and detect record; loss and queued events stay. gh_ens_export_state:
+ *   clusters [cluster0, cluster0 + n) as hb / ts [n][N][N], alive [n][N],
+ *   round [n], any of them NULL, with gh_export_state's two presentation
+ *   rules (an absent cell's ts is 0; with T_cleanup < 30 a tombstone older
+ *   than T_cleanup + 1 rounds exports ts = round + 1 - (T_cleanup + 1)).
+ *   Events: gh_ens_apply_events queues GH_EV_CRASH of the listed members for
+ *   the next round run (step 0), in one cluster or with cluster = -1 in every
+ *   cluster. Any GH_EV_JOIN / GH_EV_LEAVE (or unknown kind) in the list:
+ *   GH_EINVAL, and nothing of the list is queued.
+ *   Rounds: gh_ens_step runs `rounds` >= 0 rounds of every cluster, steps 0-6a
+ *   in SPEC order: events; REMOVE delivery to every running row but a sole
+ *   detector; the <min_members guard (a guarded row stamps ts = r on its
+ *   listed members, skips steps 3-5, still receives); own heartbeat; detect
+ *   (c != i, hb > 1, ts < r - T_fail); clean (ts < r - T_cleanup); pull merge
+ *   from the snapshot of the k peers Philox(seed; i, r, 'PEER', t / 4)[t % 4]
+ *   -> other_i. stats (may be NULL) [B]: s = exactly an engine's
+ *   gh_round_stats summed over the call (ring_empty is 0); false_failed = sum
+ *   over rounds of the running members detected, false_detections = those
+ *   members' detecting cells (gh_journal_round's fields, summed); sent /
+ *   dropped = step 6a's counters over this call.
+ *   Loss: gh_ens_set_loss takes out_q32 / in_q32 [B][N] (NULL = that side all
+ *   zero); hit(), B(a, r, blk) and the pull-mode rule are gh_set_loss's, under
+ *   the cluster's own seed. sent / dropped are always counted; with every
+ *   threshold zero each table and statistic equals the lossless run. Loss is
+ *   configuration: it persists across import and gh_ens_init_full.
+ *   gh_ens_read_failed: the last round's D_r per cluster as bitmaps
+ *   [B][ceil(N / 32)] (all zero after an import). gh_ens_read_detect, [B][N]
+ *   each, either NULL: first_round[b][c] = the first round since the last
+ *   import / gh_ens_init_full of cluster b in which c was detected while not
+ *   running (-1: never); fp_rounds[b][c] = the rounds in which c was detected
+ *   while running (the journal's definitions).
+ * Errors: GH_EINVAL, before any device is touched, for a NULL handle, cfg or
+ * params, N outside 2..128, B < 1, fanout outside 1..8, a negative
+ * min_members / t_fail / t_cleanup / rounds / round, a cluster or member id
+ * out of range. gh_ens_step returns GH_ERANGE and runs nothing when for some
+ * cluster (the largest imported or initial hb) + (rounds run since) + rounds,
+ * or its round counter + rounds, would pass INT32_MAX. GH_ENODEV without a
+ * gfx950 device: as everywhere, no CPU fallback. A failed gh_ens_create leaves
+ * *h NULL.
+ * HBM: 8 B N^2 bytes of tables + 26 B N + 132 B bytes. A handle owns its own
+ * buffers and stream; nothing is allocated, launched or changed for ordinary
+ * engines. Additive under ABI 7. */
+#define GH_ENS_MAX_MEMBERS 128
+typedef struct gh_ens_config {
+  int32_t n_members;     /* N, 2..GH_ENS_MAX_MEMBERS, the same for every cluster */
+  int32_t n_clusters;    /* B >= 1                                           */
+  int32_t fanout;        /* k, 1..8                                          */
+  int32_t min_members;   /* the <4 guard (slave/slave.go:504), >= 0          */
+  int32_t device;        /* HIP device ordinal                               */
+  int32_t reserved[3];
+} gh_ens_config;
+typedef struct gh_ens_params {   /* per cluster, 16 bytes */
+  uint64_t seed;         /* Philox key of the cluster's peer and link draws  */
+  int32_t t_fail;        /* PERIOD in rounds, >= 0                           */
+  int32_t t_cleanup;     /* COOLDOWN in rounds, >= 0                         */
+} gh_ens_params;
+typedef struct gh_ens_stats {    /* per cluster, 14 x int64 */
+  gh_round_stats s;         /* exactly an engine's, summed over the call     */
+  int64_t false_failed;     /* Σ_rounds running members detected that round  */
+  int64_t false_detections; /* those members' detecting cells                */
+  int64_t sent;             /* gossip messages of this call (step 6a)        */
+  int64_t dropped;          /* the dropped ones                              */
+} gh_ens_stats;
+int gh_ens_create(const gh_ens_config* cfg, const gh_ens_params* params, void** h);
+void gh_ens_destroy(void* h);
+const char* gh_ens_last_error(void* h);
+int gh_ens_init_full(void* h, int32_t hb0, int32_t ts0, int32_t round);
+int gh_ens_import_state(void* h, int64_t cluster, const int32_t* hb, const int32_t* ts,
+                        const uint8_t* alive, int32_t round);
+int gh_ens_export_state(void* h, int64_t cluster0, int64_t n, int32_t* hb, int32_t* ts,
+                        uint8_t* alive, int32_t* round);
+int gh_ens_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32);
+int gh_ens_apply_events(void* h, int64_t cluster, const gh_event* ev, int64_t n);
+int gh_ens_step(void* h, int32_t rounds, gh_ens_stats* stats);
+int gh_ens_read_failed(void* h, uint32_t* bitmap);
+int gh_ens_read_detect(void* h, int32_t* first_round, int32_t* fp_rounds);
+
 #ifdef __cplusplus
 }
 #endif

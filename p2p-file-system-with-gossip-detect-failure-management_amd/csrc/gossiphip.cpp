@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "comm.h"
+#include "ensemble.h"
 #include "gh_internal.h"
 
 namespace {
@@ -3598,6 +3599,356 @@ int gh_sync(void* h) {
   if (!e) return GH_EINVAL;
   HIPCHK(e, hipSetDevice(e->cfg.device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+}  // extern "C"
+
+// ---- cluster ensembles (gh_ens_*, SPEC §11; ensemble.hip) ---------------------
+// A handle of its own: B clusters' exact tables in HBM (ensemble.h), one
+// stream, and the host's mirrors of what it alone decides (each cluster's
+// round and heartbeat bound, the queued crashes). Nothing of an Engine.
+namespace {
+
+struct Ensemble {
+  gh_ens_config cfg{};
+  int32_t n = 0;
+  int64_t nb = 0;
+  std::string err;
+  hipStream_t stream = nullptr;
+  std::vector<void*> allocs;
+  GhEns d{};
+  uint32_t *out = nullptr, *in = nullptr;  // (d's are const)
+  gh_ens_params* par = nullptr;
+  int grid = 1;
+  std::vector<gh_ens_params> params;
+  std::vector<int32_t> round;     // [B] last completed round
+  std::vector<int64_t> hb_bound;  // [B] no heartbeat of the cluster is above it
+  std::vector<uint8_t> crashq;    // [B][N] crashes queued for the next round run
+  bool crash_dirty = false;
+};
+
+int ens_err(Ensemble* e, int code, const std::string& msg) {
+  e->err = msg;
+  return code;
+}
+
+#define ENSCHK(e, call)                                                                        \
+  do {                                                                                         \
+    hipError_t _st = (call);                                                                   \
+    if (_st != hipSuccess)                                                                     \
+      return ens_err((e), GH_EHIP, std::string(#call) + ": " + hipGetErrorString(_st));        \
+  } while (0)
+
+template <typename T>
+int ens_alloc(Ensemble* e, T** p, int64_t count) {
+  void* q = nullptr;
+  if (hipMalloc(&q, sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
+    (void)hipGetLastError();
+    return ens_err(e, GH_ENOMEM, "hipMalloc of " + std::to_string(sizeof(T) * count) + " bytes failed");
+  }
+  e->allocs.push_back(q);
+  *p = static_cast<T*>(q);
+  return GH_OK;
+}
+
+void ens_free(Ensemble* e) {
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  for (void* p : e->allocs) (void)hipFree(p);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+}
+
+// Clears cluster b's pending REMOVE set and detect record (import / init_full);
+// b < 0: every cluster's.
+int ens_clear_record(Ensemble* e, int64_t b) {
+  const int64_t off = b < 0 ? 0 : b * e->n, cnt = b < 0 ? e->nb * e->n : e->n;
+  ENSCHK(e, hipMemsetAsync(e->d.det_cnt + off, 0, sizeof(int32_t) * cnt, e->stream));
+  ENSCHK(e, hipMemsetAsync(e->d.fp + off, 0, sizeof(int32_t) * cnt, e->stream));
+  gh_ens_fill(e->d.det_min + off, cnt, e->n, e->stream);
+  gh_ens_fill(e->d.first + off, cnt, -1, e->stream);
+  ENSCHK(e, hipGetLastError());
+  return GH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gh_ens_create(const gh_ens_config* cfg, const gh_ens_params* params, void** h) {
+  if (h) *h = nullptr;
+  if (!h || !cfg || !params) return GH_EINVAL;
+  if (cfg->n_members < 2 || cfg->n_members > GH_ENS_MAX_MEMBERS || cfg->n_clusters < 1) return GH_EINVAL;
+  if (cfg->fanout < 1 || cfg->fanout > GH_MAXK || cfg->min_members < 0) return GH_EINVAL;
+  for (int64_t b = 0; b < cfg->n_clusters; ++b)
+    if (params[b].t_fail < 0 || params[b].t_cleanup < 0) return GH_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device || cfg->device < 0) {
+    (void)hipGetLastError();
+    return GH_ENODEV;
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return GH_ENODEV;
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GH_ENODEV;
+  if (hipSetDevice(cfg->device) != hipSuccess) return GH_ENODEV;
+
+  Ensemble* e = new Ensemble();
+  e->cfg = *cfg;
+  e->n = cfg->n_members;
+  e->nb = cfg->n_clusters;
+  e->params.assign(params, params + e->nb);
+  e->round.assign(e->nb, 0);
+  e->hb_bound.assign(e->nb, 0);
+  e->crashq.assign(e->nb * e->n, 0);
+  const int64_t cells = e->nb * e->n * e->n, vec = e->nb * e->n;
+  int rc = GH_OK;
+  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) rc = GH_EHIP;
+  if (!rc) rc = ens_alloc(e, &e->d.hb, cells);
+  if (!rc) rc = ens_alloc(e, &e->d.ts, cells);
+  if (!rc) rc = ens_alloc(e, &e->d.alive, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.crashq, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.det_cnt, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.det_min, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.first, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.fp, vec);
+  if (!rc) rc = ens_alloc(e, &e->out, vec);
+  if (!rc) rc = ens_alloc(e, &e->in, vec);
+  if (!rc) rc = ens_alloc(e, &e->d.round, e->nb);
+  if (!rc) rc = ens_alloc(e, &e->par, e->nb);
+  if (!rc) rc = ens_alloc(e, &e->d.st, e->nb * GH_ENS_NSTAT);
+  if (rc) {
+    ens_free(e);
+    return rc;
+  }
+  e->d.n = e->n;
+  e->d.k = cfg->fanout;
+  e->d.min_members = cfg->min_members;
+  e->d.nb = e->nb;
+  e->d.out = e->out;
+  e->d.in = e->in;
+  e->d.par = e->par;
+  // every cluster starts empty: all cells absent, nobody running, round 0
+  bool ok = hipMemcpyAsync(e->par, params, sizeof(gh_ens_params) * e->nb, hipMemcpyHostToDevice, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->d.hb, 0xFF, sizeof(int32_t) * cells, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->d.ts, 0, sizeof(int32_t) * cells, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->d.alive, 0, vec, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->d.crashq, 0, vec, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->out, 0, sizeof(uint32_t) * vec, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->in, 0, sizeof(uint32_t) * vec, e->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(e->d.round, 0, sizeof(int32_t) * e->nb, e->stream) == hipSuccess;
+  ok = ok && ens_clear_record(e, -1) == GH_OK;
+  ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
+  if (!ok) {
+    ens_free(e);
+    return GH_EHIP;
+  }
+  // one workgroup per cluster, as many as the card holds at once; the kernel
+  // loops when B exceeds them
+  const int64_t resident = (int64_t)prop.multiProcessorCount * gh_ens_blocks_per_cu(gh_ens_bucket(e->n));
+  e->grid = (int)std::max<int64_t>(1, std::min<int64_t>(e->nb, resident));
+  // GH_ENS_GRID caps the workgroups (results do not depend on it; the tests use it to walk the cluster loop)
+  if (const char* v = std::getenv("GH_ENS_GRID")) e->grid = std::max(1, std::min(e->grid, std::atoi(v)));
+  *h = e;
+  return GH_OK;
+}
+
+void gh_ens_destroy(void* h) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return;
+  (void)hipSetDevice(e->cfg.device);
+  ens_free(e);
+}
+
+const char* gh_ens_last_error(void* h) { return h ? static_cast<Ensemble*>(h)->err.c_str() : "null handle"; }
+
+int gh_ens_init_full(void* h, int32_t hb0, int32_t ts0, int32_t round) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (hb0 < 0) return ens_err(e, GH_ERANGE, "hb0 below 0");
+  if (round < 0) return ens_err(e, GH_EINVAL, "round below 0");
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  const int64_t cells = e->nb * e->n * e->n;
+  gh_ens_fill(e->d.hb, cells, hb0, e->stream);
+  gh_ens_fill(e->d.ts, cells, ts0, e->stream);
+  gh_ens_fill(e->d.round, e->nb, round, e->stream);
+  ENSCHK(e, hipGetLastError());
+  ENSCHK(e, hipMemsetAsync(e->d.alive, 1, e->nb * e->n, e->stream));
+  int rc;
+  if ((rc = ens_clear_record(e, -1))) return rc;
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  std::fill(e->round.begin(), e->round.end(), round);
+  std::fill(e->hb_bound.begin(), e->hb_bound.end(), (int64_t)hb0);
+  return GH_OK;
+}
+
+int gh_ens_import_state(void* h, int64_t cluster, const int32_t* hb, const int32_t* ts, const uint8_t* alive,
+                        int32_t round) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (cluster < 0 || cluster >= e->nb) return ens_err(e, GH_EINVAL, "cluster out of range");
+  if (!hb || !ts || !alive) return ens_err(e, GH_EINVAL, "null buffer");
+  if (round < 0) return ens_err(e, GH_EINVAL, "round below 0");
+  const int64_t cells = (int64_t)e->n * e->n;
+  int64_t top = 0;
+  for (int64_t x = 0; x < cells; ++x) {
+    if (hb[x] < GH_TOMBSTONE) return ens_err(e, GH_ERANGE, "hb value below -2");
+    top = std::max<int64_t>(top, hb[x]);
+  }
+  std::vector<uint8_t> al(e->n);
+  for (int32_t m = 0; m < e->n; ++m) al[m] = alive[m] != 0;
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  ENSCHK(e, hipMemcpyAsync(e->d.hb + cluster * cells, hb, sizeof(int32_t) * cells, hipMemcpyHostToDevice, e->stream));
+  ENSCHK(e, hipMemcpyAsync(e->d.ts + cluster * cells, ts, sizeof(int32_t) * cells, hipMemcpyHostToDevice, e->stream));
+  ENSCHK(e, hipMemcpyAsync(e->d.alive + cluster * e->n, al.data(), e->n, hipMemcpyHostToDevice, e->stream));
+  ENSCHK(e, hipMemcpyAsync(e->d.round + cluster, &round, sizeof round, hipMemcpyHostToDevice, e->stream));
+  int rc;
+  if ((rc = ens_clear_record(e, cluster))) return rc;
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  e->round[cluster] = round;
+  e->hb_bound[cluster] = top;
+  return GH_OK;
+}
+
+int gh_ens_export_state(void* h, int64_t cluster0, int64_t n, int32_t* hb, int32_t* ts, uint8_t* alive,
+                        int32_t* round) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (cluster0 < 0 || n < 0 || cluster0 + n > e->nb) return ens_err(e, GH_EINVAL, "cluster range");
+  const int64_t cells = (int64_t)e->n * e->n;
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  // the ts presentation rules read the heartbeats
+  std::vector<int32_t> tmp;
+  const int32_t* hsrc = hb;
+  if (ts && !hb) {
+    tmp.resize(n * cells);
+    hsrc = tmp.data();
+  }
+  if (hb || ts)
+    ENSCHK(e, hipMemcpyAsync(const_cast<int32_t*>(hsrc), e->d.hb + cluster0 * cells, sizeof(int32_t) * n * cells,
+                             hipMemcpyDeviceToHost, e->stream));
+  if (ts)
+    ENSCHK(e, hipMemcpyAsync(ts, e->d.ts + cluster0 * cells, sizeof(int32_t) * n * cells, hipMemcpyDeviceToHost,
+                             e->stream));
+  if (alive)
+    ENSCHK(e, hipMemcpyAsync(alive, e->d.alive + cluster0 * e->n, n * e->n, hipMemcpyDeviceToHost, e->stream));
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  if (ts) {
+    // gh_export_state's presentation (SPEC §1): an absent cell's ts is 0; with
+    // T_cleanup < 30 a tombstone older than T_cleanup + 1 shows that age
+    for (int64_t b = 0; b < n; ++b) {
+      const int32_t tc = e->params[cluster0 + b].t_cleanup;
+      const int64_t now = (int64_t)e->round[cluster0 + b] + 1;
+      for (int64_t x = b * cells; x < (b + 1) * cells; ++x) {
+        if (hsrc[x] == GH_ABSENT)
+          ts[x] = 0;
+        else if (hsrc[x] == GH_TOMBSTONE && tc < GH_TSAT_T && now - ts[x] > (int64_t)tc + 1)
+          ts[x] = (int32_t)(now - (tc + 1));
+      }
+    }
+  }
+  if (round)
+    for (int64_t b = 0; b < n; ++b) round[b] = e->round[cluster0 + b];
+  return GH_OK;
+}
+
+int gh_ens_set_loss(void* h, const uint32_t* out_q32, const uint32_t* in_q32) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  const size_t bytes = sizeof(uint32_t) * (size_t)(e->nb * e->n);
+  if (out_q32)
+    ENSCHK(e, hipMemcpyAsync(e->out, out_q32, bytes, hipMemcpyHostToDevice, e->stream));
+  else
+    ENSCHK(e, hipMemsetAsync(e->out, 0, bytes, e->stream));
+  if (in_q32)
+    ENSCHK(e, hipMemcpyAsync(e->in, in_q32, bytes, hipMemcpyHostToDevice, e->stream));
+  else
+    ENSCHK(e, hipMemsetAsync(e->in, 0, bytes, e->stream));
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+int gh_ens_apply_events(void* h, int64_t cluster, const gh_event* ev, int64_t n) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (cluster < -1 || cluster >= e->nb) return ens_err(e, GH_EINVAL, "cluster out of range");
+  if (n < 0 || (n > 0 && !ev)) return ens_err(e, GH_EINVAL, "bad event list");
+  for (int64_t x = 0; x < n; ++x) {
+    if (ev[x].kind != GH_EV_CRASH) return ens_err(e, GH_EINVAL, "an ensemble takes GH_EV_CRASH events only");
+    if (ev[x].member < 0 || ev[x].member >= e->n) return ens_err(e, GH_EINVAL, "event member");
+  }
+  const int64_t b0 = cluster < 0 ? 0 : cluster, b1 = cluster < 0 ? e->nb : cluster + 1;
+  for (int64_t b = b0; b < b1; ++b)
+    for (int64_t x = 0; x < n; ++x) e->crashq[b * e->n + ev[x].member] = 1;
+  if (n > 0) e->crash_dirty = true;
+  return GH_OK;
+}
+
+int gh_ens_step(void* h, int32_t rounds, gh_ens_stats* stats) {
+  static_assert(sizeof(gh_ens_stats) == GH_ENS_NSTAT * sizeof(int64_t), "gh_ens_stats is 14 int64");
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (rounds < 0) return ens_err(e, GH_EINVAL, "rounds below 0");
+  // a heartbeat grows by at most one per round: refuse the whole call when
+  // some cluster's bound (or its round counter) would pass INT32_MAX
+  for (int64_t b = 0; b < e->nb; ++b)
+    if (e->hb_bound[b] + rounds > INT32_MAX || (int64_t)e->round[b] + rounds > INT32_MAX)
+      return ens_err(e, GH_ERANGE, "cluster " + std::to_string(b) + ": a heartbeat or the round would pass INT32_MAX");
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  ENSCHK(e, hipMemsetAsync(e->d.st, 0, sizeof(int64_t) * GH_ENS_NSTAT * e->nb, e->stream));
+  if (rounds > 0) {
+    if (e->crash_dirty)
+      ENSCHK(e, hipMemcpyAsync(e->d.crashq, e->crashq.data(), e->crashq.size(), hipMemcpyHostToDevice, e->stream));
+    for (int32_t left = rounds; left > 0;) {
+      const int32_t now = std::min<int32_t>(left, GH_ENS_LAUNCH_ROUNDS);
+      ENSCHK(e, gh_ens_launch(e->d, now, e->grid, e->stream));
+      left -= now;
+    }
+    if (e->crash_dirty) {
+      ENSCHK(e, hipMemsetAsync(e->d.crashq, 0, e->crashq.size(), e->stream));
+      std::fill(e->crashq.begin(), e->crashq.end(), 0);
+      e->crash_dirty = false;
+    }
+  }
+  if (stats && rounds > 0)
+    ENSCHK(e, hipMemcpyAsync(stats, e->d.st, sizeof(gh_ens_stats) * e->nb, hipMemcpyDeviceToHost, e->stream));
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  for (int64_t b = 0; b < e->nb; ++b) {
+    e->round[b] += rounds;
+    e->hb_bound[b] += rounds;
+  }
+  if (stats && rounds == 0)
+    for (int64_t b = 0; b < e->nb; ++b) {
+      std::memset(&stats[b], 0, sizeof stats[b]);
+      stats[b].s.last_round = e->round[b];
+    }
+  return GH_OK;
+}
+
+int gh_ens_read_failed(void* h, uint32_t* bitmap) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  if (!bitmap) return ens_err(e, GH_EINVAL, "null buffer");
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  std::vector<int32_t> cnt(e->nb * e->n);
+  ENSCHK(e, hipMemcpyAsync(cnt.data(), e->d.det_cnt, sizeof(int32_t) * cnt.size(), hipMemcpyDeviceToHost, e->stream));
+  ENSCHK(e, hipStreamSynchronize(e->stream));
+  const int64_t words = (e->n + 31) / 32;
+  std::fill(bitmap, bitmap + e->nb * words, 0u);
+  for (int64_t b = 0; b < e->nb; ++b)
+    for (int32_t c = 0; c < e->n; ++c)
+      if (cnt[b * e->n + c] > 0) bitmap[b * words + (c >> 5)] |= 1u << (c & 31);
+  return GH_OK;
+}
+
+int gh_ens_read_detect(void* h, int32_t* first_round, int32_t* fp_rounds) {
+  Ensemble* e = static_cast<Ensemble*>(h);
+  if (!e) return GH_EINVAL;
+  ENSCHK(e, hipSetDevice(e->cfg.device));
+  const size_t bytes = sizeof(int32_t) * (size_t)(e->nb * e->n);
+  if (first_round) ENSCHK(e, hipMemcpyAsync(first_round, e->d.first, bytes, hipMemcpyDeviceToHost, e->stream));
+  if (fp_rounds) ENSCHK(e, hipMemcpyAsync(fp_rounds, e->d.fp, bytes, hipMemcpyDeviceToHost, e->stream));
+  ENSCHK(e, hipStreamSynchronize(e->stream));
   return GH_OK;
 }
 

@@ -34,7 +34,7 @@ from ._abi import (GH_AUDIT_BINS, GH_AVAIL_ALIVE, GH_COMM_LOCAL, GH_COMM_RCCL, G
                    GH_JOURNAL_BINS, GH_JOURNAL_DETECT, GH_JOURNAL_OFF, GH_JOURNAL_VIEWS,
                    GH_LOSS_ALWAYS, GH_LOSS_NEVER, GH_PART_SIDES, GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN)
 
-__all__ = ["Engine", "ShardGroup", "Cluster", "Census", "Groups", "FileAudit", "Journal", "GossipError", "default_config",
+__all__ = ["Engine", "Ensemble", "ShardGroup", "Cluster", "Census", "Groups", "FileAudit", "Journal", "GossipError", "default_config",
            "comm_unique_id", "Config", "GH_JOURNAL_OFF", "GH_JOURNAL_DETECT", "GH_JOURNAL_VIEWS",
            "GH_JOURNAL_BINS", "GH_LOSS_NEVER", "GH_LOSS_ALWAYS", "GH_PART_SIDES", "GH_CTL_REMOVE", "GH_CTL_LEAVE", "GH_CTL_JOIN",
            "CONTROL_LOSS_STATS"]
@@ -662,6 +662,135 @@ class Engine:
 
     def sync(self):
         self._chk(self.lib.gh_sync(self.h))
+
+
+class Ensemble:
+    """B independent small clusters behind one gh_ens_* handle (SPEC §11): the
+    same N (2..128), fanout and min_members; seeds, t_fail and t_cleanup a
+    scalar for every cluster or [B] per cluster. One workgroup owns one
+    cluster and a step(R) is one launch whatever R. Each cluster is bit for
+    bit an Engine of its seed and timeouts in pull mode, canonical detection,
+    GH_REMOVE_ALL, crash events and set_loss links. seeds=None: 0x5EED0001 +
+    the cluster's index."""
+
+    def __init__(self, n, clusters, fanout=3, seeds=None, t_fail=5, t_cleanup=5, min_members=4, device=0):
+        self.lib = _abi.load()
+        self.n, self.B = int(n), int(clusters)
+        if self.B < 1:
+            raise GossipError(_abi.GH_EINVAL, "an ensemble holds at least one cluster")
+        if seeds is None:
+            seeds = 0x5EED0001 + np.arange(self.B, dtype=np.uint64)
+        par = np.zeros(self.B, np.dtype([("seed", np.uint64), ("t_fail", np.int32), ("t_cleanup", np.int32)]))
+        par["seed"] = np.broadcast_to(np.asarray(seeds, np.uint64), (self.B,))
+        par["t_fail"] = np.broadcast_to(np.asarray(t_fail, np.int32), (self.B,))
+        par["t_cleanup"] = np.broadcast_to(np.asarray(t_cleanup, np.int32), (self.B,))
+        self.params = par
+        self.cfg = _abi.EnsConfig(self.n, self.B, fanout, min_members, device)
+        h = C.c_void_p()
+        rc = self.lib.gh_ens_create(C.byref(self.cfg), par.ctypes.data_as(C.POINTER(_abi.EnsParams)), C.byref(h))
+        if rc != GH_OK:
+            raise GossipError(rc, "gh_ens_create failed (N in 2..128, fanout in 1..8; a gfx950 device is required)")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gh_ens_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != GH_OK:
+            raise GossipError(rc, self.lib.gh_ens_last_error(self.h).decode())
+
+    def init_full(self, hb0=2, ts0=0, round_=0):
+        """Every cluster: every row alive and holding every member at (hb0, ts0)."""
+        self._chk(self.lib.gh_ens_init_full(self.h, hb0, ts0, round_))
+
+    def import_state(self, cluster, hb, ts, alive, round_=0):
+        """One cluster's tables [N][N], [N][N] and alive [N]."""
+        hb = np.ascontiguousarray(hb, dtype=np.int32)
+        ts = np.ascontiguousarray(ts, dtype=np.int32)
+        alive = np.ascontiguousarray(alive, dtype=np.uint8)
+        if hb.shape != (self.n, self.n) or ts.shape != (self.n, self.n) or alive.shape != (self.n,):
+            raise ValueError("a cluster's state is hb [N][N], ts [N][N], alive [N]")
+        self._chk(self.lib.gh_ens_import_state(self.h, cluster, _p(hb), _p(ts), _p(alive), round_))
+
+    def export_state(self, cluster0=0, n=None):
+        """(hb [n][N][N], ts [n][N][N], alive [n][N], round [n]) of clusters
+        cluster0 .. cluster0 + n - 1 (default: to the last)."""
+        n = self.B - cluster0 if n is None else n
+        if cluster0 < 0 or n < 0 or cluster0 + n > self.B:
+            raise GossipError(_abi.GH_EINVAL, "cluster range")
+        hb = np.empty((n, self.n, self.n), np.int32)
+        ts = np.empty((n, self.n, self.n), np.int32)
+        alive = np.empty((n, self.n), np.uint8)
+        rnd = np.empty(n, np.int32)
+        self._chk(self.lib.gh_ens_export_state(self.h, cluster0, n, _p(hb), _p(ts), _p(alive), _p(rnd)))
+        return hb, ts, alive, rnd
+
+    def _loss_q32(self, p):
+        """One side of set_loss as uint32 [B][N] thresholds (Engine's q32
+        conversion); a scalar, [B] per cluster or [B][N]."""
+        if p is None:
+            return None
+        a = np.asarray(p)
+        if a.dtype != np.uint32:
+            a = a.astype(np.float64)
+            if ((a < 0) | (a > 1)).any():
+                raise ValueError("a drop rate lies in [0, 1]")
+            a = np.minimum(np.round(a * 2.0 ** 32), 0xFFFFFFFF).astype(np.uint32)
+        if a.ndim == 1 and a.shape == (self.B,):
+            a = a[:, None]
+        return np.ascontiguousarray(np.broadcast_to(a, (self.B, self.n)))
+
+    def set_loss(self, out=None, inbound=None):
+        """Lossy links of every cluster (gh_ens_set_loss): each side a float in
+        [0, 1] or raw uint32 thresholds, as a scalar, [B] or [B][N]; None =
+        never. Configuration: it persists across import_state and init_full."""
+        o, i = self._loss_q32(out), self._loss_q32(inbound)
+        self._chk(self.lib.gh_ens_set_loss(self.h, None if o is None else _p(o), None if i is None else _p(i)))
+
+    def crash(self, members, cluster=None):
+        """Queue crashes of `members` for the next round run, in one cluster or
+        (None) in every cluster."""
+        self.apply_events([(GH_EV_CRASH, int(m)) for m in np.atleast_1d(members)], cluster)
+
+    def apply_events(self, events, cluster=None):
+        """gh_ens_apply_events: (kind, member) pairs; only GH_EV_CRASH is accepted."""
+        arr = (_abi.Event * max(len(events), 1))(*[_abi.Event(k, m) for k, m in events])
+        self._chk(self.lib.gh_ens_apply_events(self.h, -1 if cluster is None else cluster, arr, len(events)))
+
+    def step(self, rounds=1):
+        """Run `rounds` rounds of every cluster in one launch; {field: int64 [B]}
+        for every gh_ens_stats field (_abi.ENS_STATS)."""
+        st = np.zeros((self.B, len(_abi.ENS_STATS)), np.int64)
+        self._chk(self.lib.gh_ens_step(self.h, rounds, _p(st)))
+        return {f: st[:, x].copy() for x, f in enumerate(_abi.ENS_STATS)}
+
+    def failed(self):
+        """uint32 [B][ceil(N / 32)]: the members detected in each cluster's last round."""
+        bm = np.zeros((self.B, (self.n + 31) // 32), np.uint32)
+        self._chk(self.lib.gh_ens_read_failed(self.h, _p(bm)))
+        return bm
+
+    def detect(self):
+        """(first_round, fp_rounds), int32 [B][N] each: the first round a stopped
+        member was detected (-1: never) and the rounds a running one was."""
+        first = np.empty((self.B, self.n), np.int32)
+        fp = np.empty((self.B, self.n), np.int32)
+        self._chk(self.lib.gh_ens_read_detect(self.h, _p(first), _p(fp)))
+        return first, fp
 
 
 def _same(a, b):

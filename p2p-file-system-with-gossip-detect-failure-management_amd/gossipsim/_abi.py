@@ -40,6 +40,7 @@ GH_JOURNAL_BINS = 64
 GH_LOSS_NEVER, GH_LOSS_ALWAYS = 0, 0xFFFFFFFF
 GH_PART_SIDES = 64
 GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN = 1, 2, 4
+GH_ENS_MAX_MEMBERS = 128
 # gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
 # environment variable GH_<NAME> that gh_create reads)
 KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
@@ -82,6 +83,25 @@ class JournalRound(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("round", "running", "failed", "false_failed")] + \
                [(n, C.c_int64) for n in ("detections", "false_detections", "stale_views", "missing_views")]
 
+
+class EnsConfig(C.Structure):
+    """gh_ens_config: the shape of a cluster ensemble (32 bytes)."""
+    _fields_ = [("n_members", C.c_int32), ("n_clusters", C.c_int32), ("fanout", C.c_int32),
+                ("min_members", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class EnsParams(C.Structure):
+    """gh_ens_params: one cluster's seed and timeouts (16 bytes)."""
+    _fields_ = [("seed", C.c_uint64), ("t_fail", C.c_int32), ("t_cleanup", C.c_int32)]
+
+
+class EnsStats(C.Structure):
+    """gh_ens_stats: one cluster's counters of a gh_ens_step call (14 x int64)."""
+    _fields_ = [("s", RoundStats)] + [(n, C.c_int64) for n in ("false_failed", "false_detections", "sent", "dropped")]
+
+
+# gh_ens_stats as 14 int64, in ABI order
+ENS_STATS = tuple(n for n, _ in RoundStats._fields_) + ("false_failed", "false_detections", "sent", "dropped")
 
 # (name, restype, argtypes) for every symbol include/gossiphip.h declares.
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -144,6 +164,17 @@ SYMBOLS = [
     ("gh_set_master", C.c_int, [_vp, C.c_int32]),
     ("gh_debug_knobs", C.c_int, [_vp, _P(_i32), _i64, _P(_i64)]),
     ("gh_footprint", C.c_int, [_P(Config), _i32, _i32, _i32, _P(_i64), _P(_i64)]),
+    ("gh_ens_create", C.c_int, [_P(EnsConfig), _P(EnsParams), _P(_vp)]),
+    ("gh_ens_destroy", None, [_vp]),
+    ("gh_ens_last_error", C.c_char_p, [_vp]),
+    ("gh_ens_init_full", C.c_int, [_vp, _i32, _i32, _i32]),
+    ("gh_ens_import_state", C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32]),
+    ("gh_ens_export_state", C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("gh_ens_set_loss", C.c_int, [_vp, _vp, _vp]),
+    ("gh_ens_apply_events", C.c_int, [_vp, _i64, _P(Event), _i64]),
+    ("gh_ens_step", C.c_int, [_vp, _i32, _vp]),
+    ("gh_ens_read_failed", C.c_int, [_vp, _vp]),
+    ("gh_ens_read_detect", C.c_int, [_vp, _vp, _vp]),
 ]
 
 _lib = None
