@@ -254,9 +254,10 @@ __device__ __forceinline__ void census_block(const GhDev& d, int cur, int32_t r,
         const int32_t lo_c = (int32_t)((cmin[m] >> sh) & 0xFFFFu), hi_c = (int32_t)((cmx1[m] >> sh) & 0xFFFFu);
         const int32_t age = (int32_t)((namax[m] >> sh) & 0xFFFFu);
         if (TIER) {
-          const int32_t B = d.base[cur][c + j] + GH_P_REF + 1;
+          // (int64: with the owner at INT32_MAX - 1 or INT32_MAX, B itself is past int32)
+          const int64_t B = (int64_t)d.base[cur][c + j] + GH_P_REF + 1;
           const int64_t sm = (int64_t)n * B - (int64_t)((csum[m] >> sh) & 0xFFFFu);
-          ca.add(cc0 + j, n, B + 1 - hi_c, B - lo_c, (unsigned long long)sm, age);
+          ca.add(cc0 + j, n, (int32_t)(B + 1 - hi_c), (int32_t)(B - lo_c), (unsigned long long)sm, age);
         } else {
           const int32_t B = d.base[cur][c + j];
           const int64_t sm = (int64_t)n * B + (int64_t)csum[j];

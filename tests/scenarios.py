@@ -229,6 +229,59 @@ def ragged_wave(n, victims=None, rejoin=True, crash=RAGGED_CRASH):
     return sched
 
 
+# The counter-offset runs (test_counter_scenario.py asserts their
+# preconditions on the oracle, test_gpu_counters.py runs them): name ->
+# (H, R0). A run starts from full_state(n, hb0=H, ts0=R0) imported at round
+# R0 and runs shifted_wave(n, R0): the ragged wave far from round 0. The
+# 4-bit tier's per-column base is the owner's heartbeat - 1000 (gh_internal.h
+# GH_BASE_LAG), so `base0` takes it through 0; `top` ends with every own
+# counter at INT32_MAX - 3; on `cap` the own counters reach INT32_MAX in
+# round 33 and round 34 is refused (GH_ERANGE).
+I32MAX = 2**31 - 1
+COUNTER_OFFSETS = {
+    "base0": (985, 0),
+    "round985": (2, 985),
+    "i16": (2**15 - 12, 2**15 - 14),
+    "u16": (2**16 - 12, 2**16 - 14),
+    "f24": (2**24 - 12, 2**24 - 14),
+    "p30": (2**30, 2**30),
+    "hb30": (2**30, 0),
+    "round30": (2, 2**30),
+    "top": (I32MAX - 43, 7),
+    "cap": (I32MAX - 33, 2**24),
+}
+CAP_ROUNDS = 33  # the rounds `cap` runs before the refusal
+# heartbeat u16 with round f24: the N = 2,048 case beside `cap`
+COUNTER_MIXED = (2**16 - 12, 2**24 - 14)
+STAGGERED_OWN = (2, 990, 2**16 - 6, 2**24 - 6, 2**30, I32MAX - 60)
+
+
+def counter_state(n, name):
+    """(hb, ts, alive, R0) of COUNTER_OFFSETS[name]"""
+    h, r0 = COUNTER_OFFSETS[name]
+    return full_state(n, hb0=h, ts0=r0) + (r0,)
+
+
+def shifted_wave(n, r0, victims=None, rejoin=True, crash=RAGGED_CRASH):
+    """ragged_wave with its rounds moved by r0"""
+    return {r0 + r: ev for r, ev in ragged_wave(n, victims, rejoin, crash).items()}
+
+
+def staggered_state(n, r0, seed):
+    """(hb, ts, alive), to import at round r0: every member running, its own
+    counter drawn from STAGGERED_OWN, every view of it lagging by 0..3 (never
+    below heartbeat 0) and 0..3 rounds old. Neighbouring columns of one
+    8-cell chunk and one 16-cell lane then have bases billions apart; only the
+    INT32_MAX - 60 columns reach the cap, 60 rounds on."""
+    rng = np.random.default_rng(seed)
+    own = np.asarray(STAGGERED_OWN, np.int64)[rng.integers(0, len(STAGGERED_OWN), n)]
+    hb = np.maximum(own[None, :] - rng.integers(0, 4, (n, n)), 0)
+    ts = r0 - rng.integers(0, 4, (n, n)).astype(np.int64)
+    np.fill_diagonal(hb, own)
+    np.fill_diagonal(ts, r0)
+    return hb.astype(np.int32), ts.astype(np.int32), np.ones(n, np.uint8)
+
+
 def masked(hb, ts):
     """ts of absent cells carries no meaning in the list model (listsim keeps
     no Member for them); compare it only where hb != -1."""

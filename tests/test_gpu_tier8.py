@@ -319,10 +319,14 @@ def test_tier_tombstones(gs, oracle_mod, t_cleanup):
         assert tier_tombs == 0
 
 
-def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True, on_create=None, per_round=None):
+def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True, on_create=None, per_round=None,
+               init=None, round0=0):
     """Runs the crash wave; returns per round (stats, tier variant, lane
     jobs) and, for one engine, the final exported state. on_create(eng)
-    runs before the import, per_round(eng, r) after each round."""
+    runs before the import, per_round(eng, r) after each round. `init` =
+    (hb, ts, alive) is imported at round `round0` (full membership at round 0
+    by default); the run is then the rounds round0 + 1 .. round0 + rounds,
+    `sched` and per_round's r in those."""
     if world > 1:
         eng = gs.ShardGroup(gs.default_config(n, shard_layout=layout, **cfg), world)
     else:
@@ -334,13 +338,13 @@ def remove_run(gs, om, n, cfg, sched, rounds, world=1, layout=0, check=True, on_
             eng.close()
             raise
     orc = om.Oracle(om.default_config(n, **cfg), threads=8) if check else None
-    hb, ts, alive = sc.full_state(n)
-    eng.import_state(hb, ts, alive, 0)
+    hb, ts, alive = sc.full_state(n) if init is None else init
+    eng.import_state(hb, ts, alive, round0)
     if orc:
-        orc.import_state(hb, ts, alive, 0)
+        orc.import_state(hb, ts, alive, round0)
     trace = []
     try:
-        for r in range(1, rounds + 1):
+        for r in range(round0 + 1, round0 + rounds + 1):
             ev = sched.get(r, [])
             if ev:
                 eng.apply_events(ev)

@@ -22,33 +22,39 @@ def failed_of(orc):
     return set(np.flatnonzero(np.unpackbits(orc.read_failed().view(np.uint8), bitorder="little")).tolist())
 
 
-def run_wave(om, n, cfg, sched, rounds=ROUNDS):
-    """The schedule on the oracle from full membership: per round (stats, the
-    failed set, max lag, max age), lag and age over the views running rows
-    hold of running members."""
+def run_wave(om, n, cfg, sched, rounds=ROUNDS, hb0=2, r0=0):
+    """The schedule on the oracle from full membership (heartbeat hb0, imported
+    at round r0; `sched` is keyed by the rounds r0 + 1 ..): per round (stats,
+    the failed set, max lag, max age), lag and age over the views running rows
+    hold of running members. A round the oracle refuses (GH_ERANGE: an own
+    counter at INT32_MAX) ends the trace."""
     orc = om.Oracle(om.default_config(n, **cfg), threads=8)
     out = []
     try:
-        orc.import_state(*sc.full_state(n), 0)
-        for r in range(1, rounds + 1):
+        orc.import_state(*sc.full_state(n, hb0=hb0, ts0=r0), r0)
+        for r in range(r0 + 1, r0 + rounds + 1):
             if sched.get(r):
                 orc.apply_events(sched[r])
-            st = orc.step(1)
+            rc, st = orc.step_rc(1)
+            if rc != 0:
+                assert rc == om.GH_ERANGE and st["rounds"] == 0, (r, rc, st)
+                break
             hb, ts, alive = orc.export_state()
             run = alive != 0
             own = hb.diagonal().astype(np.int64)
             views = run[:, None] & run[None, :] & (hb >= 0)
             lag = int(np.where(views, own[None, :] - hb, 0).max())
-            age = int(np.where(views, r - ts, 0).max())
+            age = int(np.where(views, r - ts.astype(np.int64), 0).max())
             out.append((st, failed_of(orc), lag, age))
     finally:
         orc.close()
     return out
 
 
-def assert_wave(trace, victims, what, released=True):
+def assert_wave(trace, victims, what, released=True, through=None):
     """Every victim detected, tombstones the round after a detection, releases
-    later; the running members' views inside the tier's window every round."""
+    later; the running members' views inside the tier's window every round
+    (through round `through`, where given). Rounds count from the import."""
     det_rounds = [r for r, (_, failed, _, _) in enumerate(trace, 1) if failed]
     seen = set().union(*(failed for _, failed, _, _ in trace))
     assert set(victims) <= seen, (what, sorted(set(victims) - seen))
@@ -58,7 +64,8 @@ def assert_wave(trace, victims, what, released=True):
     assert d + 1 in tomb, (what, det_rounds, tomb)
     if released:
         assert any(st["released"] > 0 for st, _, _, _ in trace[d + 1:]), what
-    lag, age = max(x[2] for x in trace), max(x[3] for x in trace)
+    window = trace[:through]
+    lag, age = max(x[2] for x in window), max(x[3] for x in window)
     print(f"{what}: detection {det_rounds}, REMOVE {tomb}, max lag {lag}, max age {age}")
     assert lag <= LAG_MAX and age <= AGE_MAX, (what, lag, age)
     return det_rounds, tomb
