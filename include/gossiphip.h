@@ -96,8 +96,10 @@ typedef struct gh_config {
   int32_t introducer;    /* INTRODUCER_ADDR, slave/slave.go:22 (0)           */
   int32_t master;        /* master row whose list is Member_list (0)        */
   int32_t device;        /* HIP device ordinal                               */
-  int32_t tile_width;    /* HBM layout: members per table tile (32, 64, 128,
-                            256; 0 = default 64), see DESIGN.md             */
+  int32_t tile_width;    /* HBM layout: members per table tile (8, 16, 32,
+                            64, 128 or 256, anything else GH_EINVAL; 0 =
+                            default: 64, 256 with the sender plane), see
+                            DESIGN.md; gh_debug_knobs reports it            */
   uint64_t seed;         /* Philox key for peers and placement draws         */
   int64_t max_files;     /* file-metadata capacity (0 = no files)            */
   int64_t wide_segments; /* slots of each wide-segment arena (HBM layout,
@@ -724,13 +726,16 @@ int gh_file_info(void* h, int64_t* slots, int32_t* shards, int64_t* held);
  * map; SLOW_GRID workgroups of the per-cell kernel; NIB_RMV, NIB_DMA REMOVE
  * on / LDS-DMA staging of the nibble path; GX_DIRECT same-device row shards
  * gather their ghosts' planes in place; TMODE the timing mode; PLANE, C8 the
- * sender plane and the 4-bit tier are kept. Writes min(n_out, GH_KNOB_COUNT)
- * values; *count (may be NULL) = GH_KNOB_COUNT. No reference counterpart. */
+ * sender plane and the 4-bit tier are kept; TILE_W the members per table tile
+ * this engine (or shard) runs with: gh_config.tile_width, or its default with
+ * and without the sender plane, or GH_TILE_W where that is set. Writes
+ * min(n_out, GH_KNOB_COUNT) values; *count (may be NULL) = GH_KNOB_COUNT. No
+ * reference counterpart. */
 enum {
   GH_KNOB_QUIRK_ROWS = 0, GH_KNOB_JOBS_FLAT, GH_KNOB_RMV_FULL7, GH_KNOB_DNW, GH_KNOB_NREC, GH_KNOB_SIDE,
   GH_KNOB_SIDE_ORDER, GH_KNOB_JOIN_STAMP, GH_KNOB_FORCE_SLOW, GH_KNOB_FORCE_STORM, GH_KNOB_ROUND_NT,
   GH_KNOB_ROUND_TPW, GH_KNOB_SLOW_GRID, GH_KNOB_NIB_RMV, GH_KNOB_NIB_DMA, GH_KNOB_GX_DIRECT,
-  GH_KNOB_ROUND_XMAP, GH_KNOB_TMODE, GH_KNOB_PLANE, GH_KNOB_C8, GH_KNOB_COUNT
+  GH_KNOB_ROUND_XMAP, GH_KNOB_TMODE, GH_KNOB_PLANE, GH_KNOB_C8, GH_KNOB_TILE_W, GH_KNOB_COUNT
 };
 int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count);
 /* The HBM one shard (rank of world, layout and sizes from cfg) would hold,

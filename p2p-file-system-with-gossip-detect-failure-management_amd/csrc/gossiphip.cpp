@@ -3589,6 +3589,7 @@ int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count) {
   v[GH_KNOB_TMODE] = e->tmode;
   v[GH_KNOB_PLANE] = e->plane;
   v[GH_KNOB_C8] = e->c8;
+  v[GH_KNOB_TILE_W] = e->d.tw;
   for (int64_t i = 0; i < std::min<int64_t>(n_out, GH_KNOB_COUNT); ++i) out[i] = v[i];
   if (count) *count = GH_KNOB_COUNT;
   return GH_OK;

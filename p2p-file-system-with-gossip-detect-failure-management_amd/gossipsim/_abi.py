@@ -45,7 +45,7 @@ GH_ENS_MAX_MEMBERS = 128
 # environment variable GH_<NAME> that gh_create reads)
 KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
          "FORCE_STORM", "ROUND_NT", "ROUND_TPW", "SLOW_GRID", "NIB_RMV", "NIB_DMA", "GX_DIRECT", "ROUND_XMAP",
-         "TMODE", "PLANE", "C8")
+         "TMODE", "PLANE", "C8", "TILE_W")
 
 
 class Config(C.Structure):

@@ -229,6 +229,47 @@ def ragged_wave(n, victims=None, rejoin=True, crash=RAGGED_CRASH):
     return sched
 
 
+# The tile-width runs (test_tile_width_scenario.py asserts their preconditions
+# on the oracle, test_gpu_tile_widths.py runs them): every value
+# gh_config.tile_width takes, and the two below the plane's default of 256 at
+# which an engine with the sender plane still keeps the 4-bit tier.
+TILE_WIDTHS = (8, 16, 32, 64, 128, 256)
+TIER_WIDTHS = (64, 128)
+WIDTH_NS = (263, 1000)  # the wave's sizes at TIER_WIDTHS
+WIDTH_N = 300           # the 16-bit form's size: no multiple of 8, a partial last tile at every width
+# ... (label, world, layout) of the sharded runs at N = 263 and at WIDTH_N
+WIDTH_SHARDS = [("cols3", 3, 0), ("rows2", 2, 1)]
+
+
+def tile_bounds(n, tw):
+    """First member of the second and of the last tile of `tw` members (64 and
+    256 at n = 263, tw = 64; 128 and 896 at n = 1,000, tw = 128)."""
+    return sorted(b for b in {tw, tw * ((n - 1) // tw)} if 0 < b < n)
+
+
+def width_victims(n, tw, world=1, layout=0):
+    """tail_members(n) with both sides of the first and of the last tile
+    boundary of width `tw` and of every shard boundary."""
+    return tail_members(n, tile_bounds(n, tw) + (shard_bounds(n, world, layout) if world > 1 else []))
+
+
+def width_churn(n=WIDTH_N, rounds=30):
+    """(cfg, sched) of the 16-bit form's run at every tile width: seeded churn
+    under short timeouts (stopped rows, tombstones, absent cells, releases)."""
+    cfg = dict(fanout=3, seed=0x5EED7100, t_fail=4, t_cleanup=6)
+    return cfg, random_churn(n, rounds, 0x7101, p_crash=0.04, p_leave=0.02, p_join=0.05)
+
+
+def width_state(n=WIDTH_N, hb0=2):
+    """full_state(n) with one column whose heartbeat stands millions above its
+    owner's in every fourth row: wide segments in a 16-bit table from the
+    import on (test_gpu_census.escape_state)."""
+    hb, ts, alive = full_state(n, hb0=hb0)
+    hb[1::4, n - 3] = 5_000_000
+    hb[n - 3, n - 3] = hb0
+    return hb, ts, alive
+
+
 # The counter-offset runs (test_counter_scenario.py asserts their
 # preconditions on the oracle, test_gpu_counters.py runs them): name ->
 # (H, R0). A run starts from full_state(n, hb0=H, ts0=R0) imported at round

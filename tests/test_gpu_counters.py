@@ -552,21 +552,22 @@ def test_counter_ring_no_plane(gs, oracle_mod, monkeypatch, name, detect_mode, r
         orc.close()
 
 
-def test_counter_append_order_ring_quirk(gs, monkeypatch):
-    """GH_ORDER_APPEND at N = 64 against live listsim from `f24`, ring mode
-    with the quirk sweep: counters, tables, failed set, detectors and every
-    row's gh_lsm order each round."""
+def append_order_ring_quirk(gs, on_create=None, **cfg_kw):
+    """The run of test_counter_append_order_ring_quirk (GH_PLANE unset by the
+    caller); `cfg_kw` adds to the engine's configuration, on_create(eng) runs
+    before the import."""
     from oracle.listsim import ListSim
     import test_gpu_list_order as lo
-    monkeypatch.delenv("GH_PLANE")
     n, rounds = 64, 40
     h, r0 = OFFSETS["f24"]
     seed = 0x5EED0C40
     sched = {r0 + r: ev for r, ev in sc.random_churn(n, rounds, 0xC2, p_crash=0.03, p_leave=0.02, p_join=0.08).items()}
     state = sc.full_state(n, hb0=h, ts0=r0)
     eng = gs.Engine(gs.default_config(n, peer_mode=gs.GH_PEER_RING, fanout=3, detect_mode=1, seed=seed,
-                                      list_order=lo.APPEND))
+                                      list_order=lo.APPEND, **cfg_kw))
     try:
+        if on_create:
+            on_create(eng)
         eng.import_state(*state, r0)
         ls = ListSim.from_dense(*state, r0, seed=seed, peer_mode="ring", fanout=3, quirk=True, order="append")
         reordered, detections = 0, 0
@@ -585,6 +586,14 @@ def test_counter_append_order_ring_quirk(gs, monkeypatch):
         assert reordered > 0 and detections > 0
     finally:
         eng.close()
+
+
+def test_counter_append_order_ring_quirk(gs, monkeypatch):
+    """GH_ORDER_APPEND at N = 64 against live listsim from `f24`, ring mode
+    with the quirk sweep: counters, tables, failed set, detectors and every
+    row's gh_lsm order each round."""
+    monkeypatch.delenv("GH_PLANE")
+    append_order_ring_quirk(gs)
 
 
 def test_counter_file_ops(gs, oracle_mod, monkeypatch):

@@ -74,7 +74,7 @@ def test_knobs_defaults(gs, monkeypatch):
     assert kn == dict(GH_QUIRK_ROWS=1, GH_JOBS_FLAT=1, GH_RMV_FULL7=1, GH_DNW=1, GH_NREC=1, GH_SIDE=1,
                       GH_SIDE_ORDER=0, GH_JOIN_STAMP=1, GH_FORCE_SLOW=0, GH_FORCE_STORM=0, GH_ROUND_NT=1,
                       GH_ROUND_TPW=1, GH_SLOW_GRID=768, GH_NIB_RMV=1, GH_NIB_DMA=0, GH_GX_DIRECT=1, GH_ROUND_XMAP=1,
-                      GH_TMODE=1, GH_PLANE=1, GH_C8=1), kn
+                      GH_TMODE=1, GH_PLANE=1, GH_C8=1, GH_TILE_W=256), kn
 
 
 ONE_ENGINE = [("GH_JOBS_FLAT", 0), ("GH_RMV_FULL7", 0), ("GH_DNW", 0), ("GH_NREC", 0), ("GH_SIDE", 0), ("GH_SIDE", 2),
