@@ -771,15 +771,36 @@ int gh_sync(void* h);
  * clusters, where an engine's round is launch overhead. No reference
  * counterpart: the nearest is running the reference cluster (main.go:27-33,
  * about ten processes) B times.
- * Every cluster advances by SPEC §2 restricted to: pull mode, canonical
- * detection, GH_ORDER_ID, GH_REMOVE_ALL (D4), GH_EV_CRASH events, the lossy
- * links of step 6a. Cluster b is bit for bit what a gh_create engine with
- * params[b]'s seed and timeouts, the same N, fanout and min_members, the same
- * crashes and gh_set_loss(out[b], in[b]) computes: tables, alive, every
- * gh_round_stats field, the failed set, sent / dropped.
- * Not supported (use an engine): ring mode, quirk detection, append order,
- * GH_REMOVE_LIST, joins and leaves, partitions, lossy control messages, files,
- * election, shards, N > 128.
+ * Every cluster advances by SPEC §2 restricted to: the ensemble's peer_mode
+ * (GH_PEER_PULL, the default, or GH_PEER_RING) and detect_mode
+ * (GH_DETECT_CANONICAL, the default, or GH_DETECT_QUIRK), GH_ORDER_ID,
+ * GH_REMOVE_ALL (D4), GH_EV_CRASH events, the lossy links of step 6a. The two
+ * modes are per ensemble, not per cluster; a config with both words 0 is the
+ * ensemble of before they existed. Cluster b is bit for bit what a gh_create
+ * engine with the same peer_mode and detect_mode, params[b]'s seed and
+ * timeouts, the same N, fanout and min_members, the same crashes and
+ * gh_set_loss(out[b], in[b]) computes: tables, alive, every gh_round_stats
+ * field (ring_empty included), the failed set, sent / dropped.
+ *   GH_PEER_RING (slave/slave.go:512-524, SPEC §2 step 6 "Ring mode", the
+ *   list in member-ID order): every running active sender s takes the present
+ *   cells of its row after steps 1-5, L of them, idx = the rank of s among
+ *   them or -1; its three targets are list[(idx-1) mod L], list[(idx+1) mod L],
+ *   list[(idx+2) mod L] (Go's truncated % plus L for negatives); L = 0 counts
+ *   one ring_empty and sends nothing. Slot q in {0,1,2} to a running target g
+ *   is a message (sent), dropped iff hit(out[b][s], B(s, r, q)[0]) ||
+ *   hit(in[b][g], B(s, r, q)[1]) under the cluster's seed. With L < 4 a sender
+ *   may target one member twice, or itself: each slot is its own message,
+ *   and the merge takes the max over the distinct arrived senders. fanout is
+ *   validated (1..8) and otherwise unused, as on an engine.
+ *   GH_DETECT_QUIRK (slave/slave.go:464-477, SPEC §4, on the ID-ordered
+ *   list of an active row i after steps 1-3): c is a candidate iff c != i,
+ *   hb > 1, ts < r - T_fail; within each run of consecutive candidates the
+ *   ones at even offsets are detected, and the list's last entry always; a
+ *   skipped candidate stays present with its stale ts and is met again next
+ *   round.
+ * Not supported (use an engine): append order, GH_REMOVE_LIST, joins and
+ * leaves, partitions, lossy control messages, files, election, shards,
+ * N > 128.
  *   State: per cluster SPEC §1's tables, alive and round, plus the pending
  *   REMOVE set D_{r-1} (per member the rows that detected it and the lowest
  *   of them). It persists between gh_ens_step calls: R calls of one round
@@ -802,16 +823,17 @@ int gh_sync(void* h);
  *   in SPEC order: events; REMOVE delivery to every running row but a sole
  *   detector; the <min_members guard (a guarded row stamps ts = r on its
  *   listed members, skips steps 3-5, still receives); own heartbeat; detect
- *   (c != i, hb > 1, ts < r - T_fail); clean (ts < r - T_cleanup); pull merge
- *   from the snapshot of the k peers Philox(seed; i, r, 'PEER', t / 4)[t % 4]
- *   -> other_i. stats (may be NULL) [B]: s = exactly an engine's
- *   gh_round_stats summed over the call (ring_empty is 0); false_failed = sum
+ *   (c != i, hb > 1, ts < r - T_fail; the quirk sweep skips some); clean
+ *   (ts < r - T_cleanup); in pull mode the merge from the snapshot of the k
+ *   peers Philox(seed; i, r, 'PEER', t / 4)[t % 4] -> other_i, in ring mode
+ *   from the senders that targeted the row. stats (may be NULL) [B]: s = exactly an engine's
+ *   gh_round_stats summed over the call (ring_empty is 0 in pull mode); false_failed = sum
  *   over rounds of the running members detected, false_detections = those
  *   members' detecting cells (gh_journal_round's fields, summed); sent /
  *   dropped = step 6a's counters over this call.
  *   Loss: gh_ens_set_loss takes out_q32 / in_q32 [B][N] (NULL = that side all
- *   zero); hit(), B(a, r, blk) and the pull-mode rule are gh_set_loss's, under
- *   the cluster's own seed. sent / dropped are always counted; with every
+ *   zero); hit(), B(a, r, blk) and the pull-mode and ring-mode rules are
+ *   gh_set_loss's, under the cluster's own seed. sent / dropped are always counted; with every
  *   threshold zero each table and statistic equals the lossless run. Loss is
  *   configuration: it persists across import and gh_ens_init_full.
  *   gh_ens_read_failed: the last round's D_r per cluster as bitmaps
@@ -821,7 +843,8 @@ int gh_sync(void* h);
  *   running (-1: never); fp_rounds[b][c] = the rounds in which c was detected
  *   while running (the journal's definitions).
  * Errors: GH_EINVAL, before any device is touched, for a NULL handle, cfg or
- * params, N outside 2..128, B < 1, fanout outside 1..8, a negative
+ * params, N outside 2..128, B < 1, fanout outside 1..8, a peer_mode or
+ * detect_mode other than the two values each has, a negative
  * min_members / t_fail / t_cleanup / rounds / round, a cluster or member id
  * out of range. gh_ens_step returns GH_ERANGE and runs nothing when for some
  * cluster (the largest imported or initial hb) + (rounds run since) + rounds,
@@ -838,7 +861,9 @@ typedef struct gh_ens_config {
   int32_t fanout;        /* k, 1..8                                          */
   int32_t min_members;   /* the <4 guard (slave/slave.go:504), >= 0          */
   int32_t device;        /* HIP device ordinal                               */
-  int32_t reserved[3];
+  int32_t peer_mode;     /* GH_PEER_PULL (0, default) | GH_PEER_RING         */
+  int32_t detect_mode;   /* GH_DETECT_CANONICAL (0, default) | GH_DETECT_QUIRK */
+  int32_t reserved[1];
 } gh_ens_config;
 typedef struct gh_ens_params {   /* per cluster, 16 bytes */
   uint64_t seed;         /* Philox key of the cluster's peer and link draws  */

@@ -22,6 +22,7 @@
 
 struct GhEns {
   int32_t n, k, min_members;
+  uint8_t ring, quirk;  // GH_PEER_RING / GH_DETECT_QUIRK: which k_ens_step runs (the layout's padding: nothing moves)
   int64_t nb;  // clusters B
   int32_t *hb, *ts;
   uint8_t *alive, *crashq;
@@ -35,12 +36,14 @@ struct GhEns {
 
 // Size bucket (the kernel's row stride in LDS) of N members: 16, 32, 64, 128.
 inline int gh_ens_bucket(int n) { return n <= 16 ? 16 : n <= 32 ? 32 : n <= 64 ? 64 : 128; }
-// LDS bytes of one workgroup of that bucket.
-size_t gh_ens_lds_bytes(int bucket);
-// Workgroups of the bucket's kernel one CU holds (the occupancy query; >= 1).
-int gh_ens_blocks_per_cu(int bucket);
+// The kernel is instantiated per (bucket, ring, quirk); the three calls below
+// dispatch on all three.
+// LDS bytes of one workgroup of that instantiation.
+size_t gh_ens_lds_bytes(int bucket, bool ring, bool quirk);
+// Workgroups of that instantiation one CU holds (the occupancy query; >= 1).
+int gh_ens_blocks_per_cu(int bucket, bool ring, bool quirk);
 // Runs `rounds` (1..GH_ENS_LAUNCH_ROUNDS) rounds of every cluster on `grid`
-// workgroups, adding the statistics to d.st.
+// workgroups in the modes d carries, adding the statistics to d.st.
 hipError_t gh_ens_launch(const GhEns& d, int32_t rounds, int grid, hipStream_t s);
 // Fills p[0, n) with v.
 void gh_ens_fill(int32_t* p, int64_t n, int32_t v, hipStream_t s);

@@ -35,6 +35,46 @@
 //      detect record and the round's failed / false-positive counts; the
 //      consumed REMOVE set and the row counts are reset.
 //   D  every cell: max over the arrived senders' snapshot rows (step 6).
+//
+// Modes (k_ens_step<NM, RING, QUIRK>; gh_ens_config.peer_mode / detect_mode).
+// <NM, false, false> is the kernel above, unchanged: every mode branch is an
+// `if constexpr` and EnsLds a function of the modes, so its code, LDS bytes,
+// registers and workgroups per CU are what they were.
+//
+// RING (SPEC §2 step 6 "Ring mode", ID order). No peers are drawn in phase A
+// and the pull inboxes s_peer / s_pk do not exist. Phase B ends with each
+// row's present mask of the SNAPSHOT (a ballot of the row's lanes: one u64
+// word, two at NM = 128) in s_pm, and clears the inbox. Phase C: thread
+// (s, q) = (tid / 3, tid % 3), tid < 3 N, of a running active sender s takes
+// L and idx by popcounts of s_pm[s], selects target g = the pos-th set bit,
+// pos = (idx - 1, idx + 1, idx + 2)[q] mod L (Go's truncated %, + L when
+// negative), and when g runs and the message is not lost (block (s, r, q))
+// sets bit s of the receiver's INBOX s_inbox[g] (u32 [NM][NM / 32], LDS
+// atomicOr); thread (s, 0) counts ring_empty when L = 0. Phase D: a cell takes
+// the max of snap[s][c] over the set bits of its row's inbox. A bitmask, not
+// the 8 slots of pull mode: with diverged lists one member can be the target
+// of every sender. The merge hazard argument holds as above, and for the
+// inbox words too: phase D only reads them and writes registers; they are
+// cleared in the NEXT round's phase B, behind that round's barrier A, which a
+// thread passes only after its phase-D reads, and set again only behind that
+// round's barrier B. s_pm is written in phase B and read in phase C of the
+// same round, two barriers before its next write.
+//
+// QUIRK (SPEC §4, ID order). Phase B takes, before anything is tombstoned,
+// each cell's candidate flag and the row's present and candidate masks (two
+// ballots). A candidate c then decides by bit arithmetic: h = the highest
+// present non-candidate bit below c (the list's start when none), o = the
+// present bits strictly between h and c (all candidates); detected iff o is
+// even or no present bit lies above c (the last entry). At NM <= 64 a row
+// lies in one wave: no LDS, no barrier. At NM = 128 a row is two waves: the
+// halves meet through s_qm behind one extra barrier (barrier Q, in the
+// <128, *, true> instantiations only: five barriers a round, the others
+// four), and phase B is split in B1 (guard, heartbeat, flags, masks) and B2
+// (detect, clean, snapshot). s_qm is written in B1 and read in B2 of the same
+// round; its next write lies behind the next round's barrier A.
+//
+// No loop here depends on a mask for its trip count: bit selection is six
+// halving steps, the inbox walk at most 32 steps per word.
 #include "ensemble.h"
 #include "gh_internal.h"
 
@@ -57,8 +97,10 @@ enum {  // gh_ens_stats as int64 [GH_ENS_NSTAT]
   ES_DROPPED
 };
 
-template <int NM>
+template <int NM, bool RING, bool QUIRK>
 struct EnsLds {
+  static constexpr int PW = NM < 64 ? 1 : NM / 64;  // u64 words of a row's member mask
+  static constexpr int IW = NM < 32 ? 1 : NM / 32;  // u32 words of a receiver's inbox
   static constexpr size_t st = 0;                                      // u64 [GH_ENS_NSTAT]
   static constexpr size_t snap = st + 8 * 16;                          // i32 [NM + 1][NM]
   static constexpr size_t cnt = snap + sizeof(int32_t) * (NM + 1) * NM;  // i32 [NM]
@@ -66,22 +108,68 @@ struct EnsLds {
   static constexpr size_t dmin = dcnt + 8 * NM;                        // i32 [2][NM]
   static constexpr size_t out = dmin + 8 * NM;                         // u32 [NM]
   static constexpr size_t in = out + 4 * NM;                           // u32 [NM]
-  static constexpr size_t pk = in + 4 * NM;                            // u8 [NM][8] arrived senders (NM: none)
-  static constexpr size_t peer = pk + 8 * NM;                          // u8 [NM][8] drawn peers
-  static constexpr size_t alive = peer + 8 * NM;                       // u8 [NM]
+  static constexpr size_t pk = in + 4 * NM;                            // pull: u8 [NM][8] arrived senders (NM: none)
+  static constexpr size_t peer = pk + (RING ? 0 : 8 * NM);             // pull: u8 [NM][8] drawn peers
+  static constexpr size_t alive = peer + (RING ? 0 : 8 * NM);          // u8 [NM]
   static constexpr size_t active = alive + NM;                         // u8 [NM]
-  static constexpr size_t bytes = active + NM;
+  static constexpr size_t pm = active + NM;                            // ring: u64 [NM][PW] the snapshot rows' present masks
+  static constexpr size_t inbox = pm + (RING ? 8 * NM * PW : 0);       // ring: u32 [NM][IW] arrived senders
+  static constexpr size_t qm = inbox + (RING ? 4 * NM * IW : 0);       // quirk, NM = 128: u64 [NM][2][2] (half; present, candidate)
+  static constexpr size_t bytes = qm + (QUIRK && NM == 128 ? 32 * NM : 0);
+  static_assert(pm % 8 == 0, "the u64 masks are aligned");
 };
 
 __device__ __forceinline__ void ens_add(unsigned long long* st, int f, uint32_t v) {
   if (v) atomicAdd(st + f, (unsigned long long)v);
 }
 
-template <int NM>
+// Quirk detection (SPEC §4) of candidate c in a row whose ID-ordered list has
+// the present mask (p0, p1) and the candidate mask (c0, c1), bit c of word
+// c / 64: detected iff the present entries between c and the nearest present
+// non-candidate below it are an even number, or c is the list's last entry.
+__device__ __forceinline__ bool ens_quirk_detects(unsigned long long p0, unsigned long long p1, unsigned long long c0,
+                                                  unsigned long long c1, int c) {
+  // the bits strictly below c (2 << 63 wraps to 0: no shift by 64 anywhere)
+  const unsigned long long b0 = c >= 64 ? ~0ull : (1ull << c) - 1ull;
+  const unsigned long long b1 = c >= 64 ? (1ull << (c - 64)) - 1ull : 0ull;
+  const unsigned long long n0 = p0 & ~c0 & b0, n1 = p1 & ~c1 & b1;
+  unsigned long long m0 = b0, m1 = b1;  // strictly between that entry and c
+  if (n1) {
+    m0 = 0;
+    m1 = b1 & ~((2ull << (63 - __clzll((long long)n1))) - 1ull);
+  } else if (n0) {
+    m0 = b0 & ~((2ull << (63 - __clzll((long long)n0))) - 1ull);
+  }
+  const int o = __popcll(p0 & m0) + __popcll(p1 & m1);
+  const unsigned long long a0 = c >= 64 ? 0ull : ~((2ull << c) - 1ull);  // the bits above c
+  const unsigned long long a1 = c >= 64 ? ~((2ull << (c - 64)) - 1ull) : ~0ull;
+  return !(o & 1) || !((p0 & a0) | (p1 & a1));
+}
+
+// The position of the pos-th set bit of m (0 <= pos < popcount(m)): six halving steps.
+__device__ __forceinline__ int ens_select_bit(unsigned long long m, int pos) {
+  int base = 0;
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) {
+    const unsigned long long low = m & ((1ull << w) - 1ull);
+    const int below = __popcll(low);
+    if (pos >= below) {
+      pos -= below;
+      m >>= w;
+      base += w;
+    } else {
+      m = low;
+    }
+  }
+  return base;
+}
+
+template <int NM, bool RING, bool QUIRK>
 __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
   constexpr int CPT = NM / 8;  // rows (cells) per thread
   constexpr int RW = NM < 64 ? NM : 64;  // lanes of a wave in one row
-  using L = EnsLds<NM>;
+  using L = EnsLds<NM, RING, QUIRK>;
+  constexpr int PW = L::PW, IW = L::IW;
   extern __shared__ __align__(16) unsigned char lds[];
   unsigned long long* s_st = reinterpret_cast<unsigned long long*>(lds + L::st);
   int32_t* s_snap = reinterpret_cast<int32_t*>(lds + L::snap);
@@ -90,10 +178,13 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
   int32_t* s_dmin = reinterpret_cast<int32_t*>(lds + L::dmin);
   uint32_t* s_out = reinterpret_cast<uint32_t*>(lds + L::out);
   uint32_t* s_in = reinterpret_cast<uint32_t*>(lds + L::in);
-  uint8_t* s_pk = lds + L::pk;
-  uint8_t* s_peer = lds + L::peer;
+  [[maybe_unused]] uint8_t* s_pk = lds + L::pk;
+  [[maybe_unused]] uint8_t* s_peer = lds + L::peer;
   uint8_t* s_alive = lds + L::alive;
   uint8_t* s_active = lds + L::active;
+  [[maybe_unused]] unsigned long long* s_pm = reinterpret_cast<unsigned long long*>(lds + L::pm);
+  [[maybe_unused]] uint32_t* s_inbox = reinterpret_cast<uint32_t*>(lds + L::inbox);
+  [[maybe_unused]] unsigned long long* s_qm = reinterpret_cast<unsigned long long*>(lds + L::qm);
 
   const int tid = threadIdx.x;
   const int n = d.n, k = d.k;
@@ -101,7 +192,9 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
   const int lane = tid & 63;
   // the lanes of this thread's row in its wave
   const unsigned long long rowmask = RW == 64 ? ~0ull : ((1ull << RW) - 1ull) << ((lane / RW) * RW);
-  const int li = tid >> 3, lt = tid & 7;  // phase C: receiver and draw
+  [[maybe_unused]] const int rsh = RW == 64 ? 0 : (lane / RW) * RW;  // the row's first lane in its wave
+  [[maybe_unused]] const int li = tid >> 3, lt = tid & 7;  // phase C, pull: receiver and draw
+  [[maybe_unused]] const int rs = tid / 3, rq = tid - 3 * rs;  // phase C, ring: sender and slot
 
   for (int64_t b = blockIdx.x; b < d.nb; b += gridDim.x) {
     const gh_ens_params par = d.par[b];
@@ -145,11 +238,12 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
     uint32_t amask = 0;  // bit j: row 8 j + ro is running
 #pragma unroll
     for (int j = 0; j < CPT; ++j) amask |= (uint32_t)(s_alive[8 * j + ro] != 0) << j;
-    const bool li_runs = lt < k && li < n && s_alive[li];
+    [[maybe_unused]] const bool li_runs = lt < k && li < n && s_alive[li];
     const bool me_runs = tid < n && s_alive[tid];
 
     uint32_t c_tomb = 0, c_unk = 0, c_det = 0, c_rel = 0, c_mrg = 0, c_act = 0;
     uint32_t c_failed = 0, c_ff = 0, c_fd = 0, c_sent = 0, c_drop = 0;
+    [[maybe_unused]] uint32_t c_empty = 0;
     int pb = 0;  // the REMOVE set pending this round
 
     for (int32_t q = 0; q < rounds; ++q) {
@@ -157,7 +251,7 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
       // r >= 1 and T >= 0: r - T fits an int32
       const int32_t r_fail = r - par.t_fail, r_clean = r - par.t_cleanup;
       // ---- phase A: peers; REMOVE delivery (step 1); row counts ---------------
-      if (me_runs) {
+      if (!RING && me_runs) {
         for (int blk = 0; 4 * blk < k; ++blk) {
           uint32_t w[4];
           gh_philox_block(par.seed, (uint32_t)tid, (uint32_t)r, GH_TAG_PEER, (uint32_t)blk, w);
@@ -189,32 +283,97 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
       }
       __syncthreads();
       // ---- phase B: guard, own heartbeat, detect, clean (steps 2-5); snapshot --
+      if constexpr (RING) {
+        if (tid < NM * IW) s_inbox[tid] = 0;  // (last round's phase D is done with it: barrier A)
+      }
+      [[maybe_unused]] uint32_t cbits = 0;  // quirk, NM = 128: bit j = the cell of row 8 j + ro is a candidate
+      if constexpr (QUIRK && NM == 128) {
+        // B1: steps 2-3 and the candidates; the row's two half masks meet in LDS
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+          if (8 * j >= n) continue;  // (uniform: rows outside N)
+          const int i = 8 * j + ro;
+          const bool run = (amask >> j) & 1u;
+          const bool act = run && s_cnt[i] >= d.min_members;
+          if (run && !act) {
+            if (hb[j] >= 0) ts[j] = r;
+          } else if (act && c == i && hb[j] >= 0) {
+            ++hb[j];
+            ts[j] = r;
+          }
+          const bool cd = act && c != i && hb[j] > 1 && ts[j] < r_fail;
+          const unsigned long long pmk = __ballot(hb[j] >= 0), cmk = __ballot(cd);
+          if (lane == 0) {
+            s_qm[4 * i + 2 * (c >> 6)] = pmk;
+            s_qm[4 * i + 2 * (c >> 6) + 1] = cmk;
+          }
+          cbits |= (uint32_t)cd << j;
+        }
+        __syncthreads();  // barrier Q
+      }
 #pragma unroll
       for (int j = 0; j < CPT; ++j) {
         if (8 * j >= n) continue;  // (uniform: rows outside N)
         const int i = 8 * j + ro;
         const bool run = (amask >> j) & 1u;
         const bool act = run && s_cnt[i] >= d.min_members;
-        if (run && !act) {
-          if (hb[j] >= 0) ts[j] = r;  // the <4 guard: the row only stamps its list
-        } else if (act) {
-          if (c == i) {
-            if (hb[j] >= 0) {
+        if constexpr (!QUIRK) {
+          if (run && !act) {
+            if (hb[j] >= 0) ts[j] = r;  // the <4 guard: the row only stamps its list
+          } else if (act) {
+            if (c == i) {
+              if (hb[j] >= 0) {
+                ++hb[j];
+                ts[j] = r;
+              }
+            } else if (hb[j] > 1 && ts[j] < r_fail) {
+              hb[j] = GH_TOMBSTONE;
+              ++c_det;
+              atomicAdd(&s_dcnt[(pb ^ 1) * NM + c], 1);
+              atomicMin(&s_dmin[(pb ^ 1) * NM + c], i);
+            }
+            if (hb[j] == GH_TOMBSTONE && ts[j] < r_clean) {
+              hb[j] = GH_ABSENT;
+              ++c_rel;
+            }
+          }
+        } else {
+          bool cd;
+          unsigned long long p0, p1 = 0, c0, c1 = 0;
+          if constexpr (NM == 128) {
+            cd = (cbits >> j) & 1u;
+            p0 = s_qm[4 * i];  // (one address per wave: a broadcast)
+            c0 = s_qm[4 * i + 1];
+            p1 = s_qm[4 * i + 2];
+            c1 = s_qm[4 * i + 3];
+          } else {
+            if (run && !act) {
+              if (hb[j] >= 0) ts[j] = r;  // the <4 guard: the row only stamps its list
+            } else if (act && c == i && hb[j] >= 0) {
               ++hb[j];
               ts[j] = r;
             }
-          } else if (hb[j] > 1 && ts[j] < r_fail) {
+            cd = act && c != i && hb[j] > 1 && ts[j] < r_fail;
+            // the row's list and its candidates, before anything is tombstoned
+            p0 = (__ballot(hb[j] >= 0) & rowmask) >> rsh;
+            c0 = (__ballot(cd) & rowmask) >> rsh;
+          }
+          if (cd && ens_quirk_detects(p0, p1, c0, c1, c)) {
             hb[j] = GH_TOMBSTONE;
             ++c_det;
             atomicAdd(&s_dcnt[(pb ^ 1) * NM + c], 1);
             atomicMin(&s_dmin[(pb ^ 1) * NM + c], i);
           }
-          if (hb[j] == GH_TOMBSTONE && ts[j] < r_clean) {
+          if (act && hb[j] == GH_TOMBSTONE && ts[j] < r_clean) {
             hb[j] = GH_ABSENT;
             ++c_rel;
           }
         }
         s_snap[8 * NM * j + tid] = hb[j];  // (= [i][c]: tid = ro * NM + c)
+        if constexpr (RING) {
+          const unsigned long long sp = __ballot(hb[j] >= 0);
+          if ((lane & (RW - 1)) == 0) s_pm[PW * i + (NM == 128 ? c >> 6 : 0)] = (sp & rowmask) >> rsh;
+        }
         if (c == 0) {
           s_active[i] = act;
           c_act += act;
@@ -222,7 +381,35 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
       }
       __syncthreads();
       // ---- phase C: which draws arrive (step 6a); the round's record ----------
-      {
+      if constexpr (RING) {
+        // thread (rs, rq): slot rq of sender rs (ring form of steps 6 and 6a)
+        if (tid < 3 * n && s_alive[rs] && s_active[rs]) {
+          const unsigned long long p0 = s_pm[PW * rs], p1 = PW > 1 ? s_pm[PW * rs + PW - 1] : 0ull;
+          const int n0 = __popcll(p0), len = n0 + __popcll(p1);
+          if (len == 0) {
+            c_empty += rq == 0;  // (the reference divides by zero here: D3)
+          } else {
+            const unsigned long long w = rs >= 64 ? p1 : p0, bit = 1ull << (rs & 63);
+            const int idx = (w & bit) ? (rs >= 64 ? n0 : 0) + __popcll(w & (bit - 1ull)) : -1;
+            int pos = (idx + (rq == 0 ? -1 : rq)) % len;  // truncated, as Go's
+            if (pos < 0) pos += len;
+            const int g = pos < n0 ? ens_select_bit(p0, pos) : 64 + ens_select_bit(p1, pos - n0);
+            if (s_alive[g]) {
+              ++c_sent;
+              bool lost = false;
+              if (lossy) {
+                uint32_t w4[4];
+                gh_philox_block(par.seed, (uint32_t)rs, (uint32_t)r, GH_TAG_LINK, (uint32_t)rq, w4);
+                lost = gh_link_hit(s_out[rs], w4[0]) || gh_link_hit(s_in[g], w4[1]);
+              }
+              if (lost)
+                ++c_drop;
+              else
+                atomicOr(&s_inbox[IW * g + (rs >> 5)], 1u << (rs & 31));
+            }
+          }
+        }
+      } else {
         int s = NM;  // no sender
         if (li_runs) {
           const int p = s_peer[8 * li + lt];
@@ -263,9 +450,21 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
 #pragma unroll
       for (int j = 0; j < CPT; ++j) {
         if (8 * j >= n) continue;  // (uniform: rows outside N)
-        const unsigned long long snd = reinterpret_cast<const unsigned long long*>(s_pk)[8 * j + ro];
         int32_t m = GH_ABSENT;
-        for (int t = 0; t < k; ++t) m = max(m, s_snap[(int)((snd >> (8 * t)) & 0xFFu) * NM + c]);
+        if constexpr (RING) {
+          // the row's inbox: one address per row, so wave-uniform at NM >= 64
+#pragma unroll
+          for (int w = 0; w < IW; ++w) {
+            uint32_t bits = s_inbox[IW * (8 * j + ro) + w];
+            for (int t = 0; t < 32 && bits; ++t) {
+              m = max(m, s_snap[(32 * w + __ffs((int)bits) - 1) * NM + c]);
+              bits &= bits - 1u;
+            }
+          }
+        } else {
+          const unsigned long long snd = reinterpret_cast<const unsigned long long*>(s_pk)[8 * j + ro];
+          for (int t = 0; t < k; ++t) m = max(m, s_snap[(int)((snd >> (8 * t)) & 0xFFu) * NM + c]);
+        }
         if (hb[j] >= GH_ABSENT && m > hb[j]) {
           hb[j] = m;
           ts[j] = r;
@@ -274,7 +473,8 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
       }
       pb ^= 1;
       // (no barrier: the next round writes s_peer and s_cnt, which phase D does
-      // not read, and reaches the snapshot and s_pk only behind its barrier A)
+      // not read, and reaches the snapshot, s_pk and the ring inbox only behind
+      // its barrier A)
     }
 
     // ---- store ----------------------------------------------------------------
@@ -297,6 +497,7 @@ __global__ __launch_bounds__(8 * NM) void k_ens_step(GhEns d, int32_t rounds) {
     ens_add(s_st, ES_FALSE_DETECTIONS, c_fd);
     ens_add(s_st, ES_SENT, c_sent);
     ens_add(s_st, ES_DROPPED, c_drop);
+    if constexpr (RING) ens_add(s_st, ES_RING_EMPTY, c_empty);
     __syncthreads();
     if (tid < n) {
       d.alive[vb + tid] = s_alive[tid];
@@ -323,51 +524,78 @@ __global__ __launch_bounds__(256) void k_ens_fill(int32_t* p, int64_t n, int32_t
     p[x] = v;
 }
 
-template <int NM>
+template <int NM, bool RING, bool QUIRK>
 hipError_t ens_prepare() {
   // above 64 KiB a kernel's dynamic LDS needs the opt-in (bucket 128)
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ens_step<NM>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)EnsLds<NM>::bytes);
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ens_step<NM, RING, QUIRK>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)EnsLds<NM, RING, QUIRK>::bytes);
 }
 
-template <int NM>
+template <int NM, bool RING, bool QUIRK>
 int ens_occupancy() {
   int nb = 0;
-  if (ens_prepare<NM>() != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ens_step<NM>, 8 * NM, EnsLds<NM>::bytes) != hipSuccess) {
+  if (ens_prepare<NM, RING, QUIRK>() != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ens_step<NM, RING, QUIRK>, 8 * NM,
+                                                   EnsLds<NM, RING, QUIRK>::bytes) != hipSuccess) {
     (void)hipGetLastError();
     nb = 1;
   }
   return nb < 1 ? 1 : nb;
 }
 
-template <int NM>
+template <int NM, bool RING, bool QUIRK>
 hipError_t ens_launch(const GhEns& d, int32_t rounds, int grid, hipStream_t s) {
-  const hipError_t rc = ens_prepare<NM>();
+  const hipError_t rc = ens_prepare<NM, RING, QUIRK>();
   if (rc != hipSuccess) return rc;
-  hipLaunchKernelGGL(k_ens_step<NM>, dim3(grid), dim3(8 * NM), EnsLds<NM>::bytes, s, d, rounds);
+  constexpr size_t lds_bytes = EnsLds<NM, RING, QUIRK>::bytes;
+  hipLaunchKernelGGL((k_ens_step<NM, RING, QUIRK>), dim3(grid), dim3(8 * NM), lds_bytes, s, d, rounds);
   return hipGetLastError();
+}
+
+// The instantiation of (bucket, ring, quirk) as a tag f is called with.
+template <int NM, bool RING, bool QUIRK>
+struct EnsInst {
+  static constexpr int nm = NM;
+  static constexpr bool ring = RING, quirk = QUIRK;
+};
+
+template <int NM, class F>
+auto ens_pick_modes(bool ring, bool quirk, F&& f) {
+  if (ring) return quirk ? f(EnsInst<NM, true, true>{}) : f(EnsInst<NM, true, false>{});
+  return quirk ? f(EnsInst<NM, false, true>{}) : f(EnsInst<NM, false, false>{});
+}
+
+template <class F>
+auto ens_pick(int bucket, bool ring, bool quirk, F&& f) {
+  switch (bucket) {
+    case 16: return ens_pick_modes<16>(ring, quirk, f);
+    case 32: return ens_pick_modes<32>(ring, quirk, f);
+    case 64: return ens_pick_modes<64>(ring, quirk, f);
+    default: return ens_pick_modes<128>(ring, quirk, f);
+  }
 }
 
 }  // namespace
 
-size_t gh_ens_lds_bytes(int bucket) {
-  return bucket == 16 ? EnsLds<16>::bytes : bucket == 32 ? EnsLds<32>::bytes : bucket == 64 ? EnsLds<64>::bytes
-                                                                                           : EnsLds<128>::bytes;
+size_t gh_ens_lds_bytes(int bucket, bool ring, bool quirk) {
+  return ens_pick(bucket, ring, quirk, [](auto t) -> size_t {
+    using T = decltype(t);
+    return EnsLds<T::nm, T::ring, T::quirk>::bytes;
+  });
 }
 
-int gh_ens_blocks_per_cu(int bucket) {
-  return bucket == 16 ? ens_occupancy<16>() : bucket == 32 ? ens_occupancy<32>() : bucket == 64 ? ens_occupancy<64>()
-                                                                                              : ens_occupancy<128>();
+int gh_ens_blocks_per_cu(int bucket, bool ring, bool quirk) {
+  return ens_pick(bucket, ring, quirk, [](auto t) -> int {
+    using T = decltype(t);
+    return ens_occupancy<T::nm, T::ring, T::quirk>();
+  });
 }
 
 hipError_t gh_ens_launch(const GhEns& d, int32_t rounds, int grid, hipStream_t s) {
-  switch (gh_ens_bucket(d.n)) {
-    case 16: return ens_launch<16>(d, rounds, grid, s);
-    case 32: return ens_launch<32>(d, rounds, grid, s);
-    case 64: return ens_launch<64>(d, rounds, grid, s);
-    default: return ens_launch<128>(d, rounds, grid, s);
-  }
+  return ens_pick(gh_ens_bucket(d.n), d.ring != 0, d.quirk != 0, [&](auto t) -> hipError_t {
+    using T = decltype(t);
+    return ens_launch<T::nm, T::ring, T::quirk>(d, rounds, grid, s);
+  });
 }
 
 void gh_ens_fill(int32_t* p, int64_t n, int32_t v, hipStream_t s) {

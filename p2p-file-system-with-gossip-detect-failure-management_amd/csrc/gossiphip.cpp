@@ -3681,6 +3681,8 @@ int gh_ens_create(const gh_ens_config* cfg, const gh_ens_params* params, void** 
   if (!h || !cfg || !params) return GH_EINVAL;
   if (cfg->n_members < 2 || cfg->n_members > GH_ENS_MAX_MEMBERS || cfg->n_clusters < 1) return GH_EINVAL;
   if (cfg->fanout < 1 || cfg->fanout > GH_MAXK || cfg->min_members < 0) return GH_EINVAL;
+  if (cfg->peer_mode != GH_PEER_PULL && cfg->peer_mode != GH_PEER_RING) return GH_EINVAL;
+  if (cfg->detect_mode != GH_DETECT_CANONICAL && cfg->detect_mode != GH_DETECT_QUIRK) return GH_EINVAL;
   for (int64_t b = 0; b < cfg->n_clusters; ++b)
     if (params[b].t_fail < 0 || params[b].t_cleanup < 0) return GH_EINVAL;
   int ndev = 0;
@@ -3724,6 +3726,8 @@ int gh_ens_create(const gh_ens_config* cfg, const gh_ens_params* params, void** 
   e->d.n = e->n;
   e->d.k = cfg->fanout;
   e->d.min_members = cfg->min_members;
+  e->d.ring = cfg->peer_mode == GH_PEER_RING;  // (fanout is validated and otherwise unused, as on an engine)
+  e->d.quirk = cfg->detect_mode == GH_DETECT_QUIRK;
   e->d.nb = e->nb;
   e->d.out = e->out;
   e->d.in = e->in;
@@ -3745,7 +3749,8 @@ int gh_ens_create(const gh_ens_config* cfg, const gh_ens_params* params, void** 
   }
   // one workgroup per cluster, as many as the card holds at once; the kernel
   // loops when B exceeds them
-  const int64_t resident = (int64_t)prop.multiProcessorCount * gh_ens_blocks_per_cu(gh_ens_bucket(e->n));
+  const int64_t resident =
+      (int64_t)prop.multiProcessorCount * gh_ens_blocks_per_cu(gh_ens_bucket(e->n), e->d.ring != 0, e->d.quirk != 0);
   e->grid = (int)std::max<int64_t>(1, std::min<int64_t>(e->nb, resident));
   // GH_ENS_GRID caps the workgroups (results do not depend on it; the tests use it to walk the cluster loop)
   if (const char* v = std::getenv("GH_ENS_GRID")) e->grid = std::max(1, std::min(e->grid, std::atoi(v)));

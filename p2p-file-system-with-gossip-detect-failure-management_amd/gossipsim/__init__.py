@@ -669,13 +669,20 @@ class Ensemble:
     same N (2..128), fanout and min_members; seeds, t_fail and t_cleanup a
     scalar for every cluster or [B] per cluster. One workgroup owns one
     cluster and a step(R) is one launch whatever R. Each cluster is bit for
-    bit an Engine of its seed and timeouts in pull mode, canonical detection,
-    GH_REMOVE_ALL, crash events and set_loss links. seeds=None: 0x5EED0001 +
-    the cluster's index."""
+    bit an Engine of its seed and timeouts with the ensemble's peer_mode
+    (GH_PEER_PULL, the default, or GH_PEER_RING: the reference's push to three
+    ring neighbours, in which fanout is validated and otherwise unused) and
+    detect_mode (GH_DETECT_CANONICAL, the default, or GH_DETECT_QUIRK: the
+    reference's skipping sweep), GH_ORDER_ID, GH_REMOVE_ALL, crash events and
+    set_loss links: tables, alive, every round statistic (ring_empty
+    included), the failed set, sent / dropped. The modes are per ensemble,
+    not per cluster. seeds=None: 0x5EED0001 + the cluster's index."""
 
-    def __init__(self, n, clusters, fanout=3, seeds=None, t_fail=5, t_cleanup=5, min_members=4, device=0):
+    def __init__(self, n, clusters, fanout=3, seeds=None, t_fail=5, t_cleanup=5, min_members=4, device=0,
+                 peer_mode=GH_PEER_PULL, detect_mode=GH_DETECT_CANONICAL):
         self.lib = _abi.load()
         self.n, self.B = int(n), int(clusters)
+        self.peer_mode, self.detect_mode = int(peer_mode), int(detect_mode)
         if self.B < 1:
             raise GossipError(_abi.GH_EINVAL, "an ensemble holds at least one cluster")
         if seeds is None:
@@ -685,11 +692,12 @@ class Ensemble:
         par["t_fail"] = np.broadcast_to(np.asarray(t_fail, np.int32), (self.B,))
         par["t_cleanup"] = np.broadcast_to(np.asarray(t_cleanup, np.int32), (self.B,))
         self.params = par
-        self.cfg = _abi.EnsConfig(self.n, self.B, fanout, min_members, device)
+        self.cfg = _abi.EnsConfig(self.n, self.B, fanout, min_members, device, self.peer_mode, self.detect_mode)
         h = C.c_void_p()
         rc = self.lib.gh_ens_create(C.byref(self.cfg), par.ctypes.data_as(C.POINTER(_abi.EnsParams)), C.byref(h))
         if rc != GH_OK:
-            raise GossipError(rc, "gh_ens_create failed (N in 2..128, fanout in 1..8; a gfx950 device is required)")
+            raise GossipError(rc, "gh_ens_create failed (N in 2..128, fanout in 1..8, peer_mode pull or ring, "
+                                  "detect_mode canonical or quirk; a gfx950 device is required)")
         self.h = h
 
     def close(self):

@@ -87,7 +87,8 @@ class JournalRound(C.Structure):
 class EnsConfig(C.Structure):
     """gh_ens_config: the shape of a cluster ensemble (32 bytes)."""
     _fields_ = [("n_members", C.c_int32), ("n_clusters", C.c_int32), ("fanout", C.c_int32),
-                ("min_members", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("min_members", C.c_int32), ("device", C.c_int32), ("peer_mode", C.c_int32),
+                ("detect_mode", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class EnsParams(C.Structure):
