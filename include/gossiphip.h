@@ -87,6 +87,10 @@ extern "C" {
 typedef struct gh_config {
   int32_t n_members;     /* N; member IDs 0..N-1                             */
   int32_t fanout;        /* k (pull mode), 1..8                              */
+                         /* k = 3..4 take the sender plane and the 4-bit tier
+                          * (slower dissemination, k < 3, leaves views outside
+                          * the plane's window); k >= 5 takes the 8-sender
+                          * round kernel (k_round<KB = 8>, k <= 4: KB = 4)     */
   int32_t peer_mode;     /* GH_PEER_PULL | GH_PEER_RING                      */
   int32_t detect_mode;   /* GH_DETECT_CANONICAL | GH_DETECT_QUIRK            */
   int32_t t_fail;        /* PERIOD in rounds, slave/slave.go:24 (5)          */

@@ -323,6 +323,103 @@ def staggered_state(n, r0, seed):
     return hb.astype(np.int32), ts.astype(np.int32), np.ones(n, np.uint8)
 
 
+# The fanout runs (test_fanout_scenario.py asserts their preconditions on the
+# oracle and on loss_ref.LossModel.peers, test_gpu_fanout.py runs them): every
+# value gh_config.fanout takes but the 3 and 4 of the rest of the suite. k >= 5
+# takes the 8-sender instantiation of the round kernel and draws 4..7 from the
+# second Philox block; k < 3 has neither the sender plane nor the 4-bit tier.
+FANOUTS = (1, 2, 5, 6, 7, 8)
+FANOUT_NS = (263, 1000)            # the wave's sizes on one engine
+FANOUT_COLLAPSE = 1                # the fanout at which the wave's cluster collapses at T_fail = 16
+FANOUT_SHARD_KS = (1, 2, 5, 8)
+# ... (label, n, world, layout) of the sharded waves
+FANOUT_SHARDS = [("cols3", 263, 3, 0), ("cols8", 250, 8, 0), ("rows2", 263, 2, 1), ("rows3", 263, 3, 1)]
+FANOUT_LOCKSTEP = ("cols3", "rows2")   # k = 8 also beside one engine
+# ... (k, tile width) of the N = WIDTH_N churn
+FANOUT_WIDTHS = [(k, tw) for k in (2, 5, 8) for tw in TILE_WIDTHS] + [(1, 8), (1, 256)]
+FANOUT_CHURN_KS = (1, 2, 5, 8)
+FANOUT_COUNTER_KS = (2, 8)         # the wave far from round 0: from `f24`, and `cap` through its refusal
+FANOUT_SEED = 0x5EED0F00
+# the seed of fanout k is FANOUT_SEED + 16 * FANOUT_SEED_STEP[k] + k: the first
+# step at which every precondition of test_fanout_scenario.py holds (at k = 8
+# the sharded inbox shapes need a receiver that draws three crashed senders in
+# its second Philox block, at k = 1 cols8's 233 survivors must all fall under
+# the guard in one round)
+FANOUT_SEED_STEP = {1: 1, 2: 0, 5: 0, 6: 0, 7: 0, 8: 5}
+
+
+def fanout_cfg(k, t=16, **kw):
+    """ragged_cfg's shape at fanout k, T_fail = T_cleanup = t, on the fanout
+    runs' own seeds; `kw` adds to or overrides the configuration."""
+    return dict(dict(fanout=k, seed=FANOUT_SEED + 16 * FANOUT_SEED_STEP[k] + k, t_fail=t, t_cleanup=t), **kw)
+
+
+def fanout_victims(n, world=1, layout=0):
+    """tail_members(n), on shards with both sides of every shard boundary."""
+    return tail_members(n, shard_bounds(n, world, layout) if world > 1 else ())
+
+
+def fanout_wave(n, world=1, layout=0, r0=0):
+    """ragged_wave of fanout_victims (crash at round 8, the last member joins
+    again at round 30), its rounds moved by r0."""
+    return shifted_wave(n, r0, fanout_victims(n, world, layout))
+
+
+def fanout_churn(k, **kw):
+    """(cfg, sched) of width_churn() at fanout k."""
+    cfg, sched = width_churn()
+    return dict(cfg, fanout=k, **kw), sched
+
+
+# The mass crash: a quarter of N = 1,000 stops at round 4 under short
+# timeouts, 24 rounds; at k = 5 the detections spread over rounds, at k = 8
+# one round detects every victim.
+MASS_N, MASS_T_FAIL, MASS_T_CLEANUP, MASS_FRAC, MASS_CRASH, MASS_ROUNDS = 1000, 6, 8, 0.25, 4, 24
+MASS_KS = (5, 8)
+MASS_SEED_STEP = {5: 0, 8: 0}      # as FANOUT_SEED_STEP, for the mass crash's own preconditions
+
+
+def fanout_mass(k):
+    """(cfg, sched, victims) of the mass crash at fanout k."""
+    cfg = fanout_cfg(k, t_fail=MASS_T_FAIL, t_cleanup=MASS_T_CLEANUP, seed=FANOUT_SEED + 16 * MASS_SEED_STEP[k] + k)
+    victims = crash_ids(MASS_N, MASS_FRAC, cfg["seed"])
+    return cfg, {MASS_CRASH: [(CRASH, int(c)) for c in victims]}, victims
+
+
+# The tiny clusters: (n, k) with N <= k + 1 at k = 8 (every receiver's draws
+# repeat senders from N <= 8 down), min_members = 2, T_fail = T_cleanup = 5,
+# the last member crashes at round 6.
+TINY_NS, TINY_KS = (2, 3, 5, 8, 9), (1, 8)
+TINY_TABLE = [(n, k) for k in TINY_KS for n in TINY_NS]
+TINY_T, TINY_CRASH, TINY_ROUNDS = 5, 6, 20
+TINY_SHARDED = (9, 8)              # (n, k) on two column shards and on two row shards
+TINY_ONE_TILE = (5, 8, (8, 256))   # (n, k, tile widths): one tile, mostly padding
+
+
+def fanout_tiny(n, k, **kw):
+    """(cfg, sched) of a tiny cluster."""
+    return fanout_cfg(k, TINY_T, min_members=2, **kw), {TINY_CRASH: [(CRASH, n - 1)]}
+
+
+# Ensembles at the fanouts ensemble_ref.GROUPS leaves out: name -> the
+# arguments of ensemble_ref.case for its two clusters (n, k, t_fail, t_cleanup,
+# rate, rounds, crash, seed); the second cluster of every group has no loss.
+FANOUT_ENSEMBLES = {
+    "n16k2": [(16, 2, 8, 8, 0.2, 24, {4: [15]}, 0x5EED0F52), (16, 2, 9, 6, 0.0, 24, {3: [0, 7]}, 0x5EED0F53)],
+    "n33k5": [(33, 5, 5, 5, 0.3, 24, {4: [1, 32]}, 0x5EED0F55), (33, 5, 4, 6, 0.0, 24, {6: [16]}, 0x5EED0F56)],
+    "n64k6": [(64, 6, 5, 5, 0.3, 24, {4: [0, 63]}, 0x5EED0F57), (64, 6, 6, 4, 0.0, 24, {5: [31, 32]}, 0x5EED0F58)],
+    "n128k7": [(128, 7, 5, 5, 0.3, 20, {4: [5, 64, 127]}, 0x5EED0F59), (128, 7, 4, 7, 0.0, 20, {3: [127]}, 0x5EED0F5A)],
+}
+
+# GH_ORDER_APPEND at k = 8: N = 100 in pull mode from a full start against
+# oracle/listsim.py (its T_fail = T_cleanup = 5), seeded churn with re-adds.
+APPEND_N, APPEND_K, APPEND_ROUNDS, APPEND_SEED = 100, 8, 30, 0x5EED0F80
+
+
+def fanout_append_churn():
+    return random_churn(APPEND_N, APPEND_ROUNDS, 0xF81, p_crash=0.03, p_leave=0.02, p_join=0.08)
+
+
 def masked(hb, ts):
     """ts of absent cells carries no meaning in the list model (listsim keeps
     no Member for them); compare it only where hb != -1."""
