@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define GH_ABI_VERSION 7
+#define GH_ABI_VERSION 8
 
 /* ---- error codes ---------------------------------------------------- */
 #define GH_OK 0
@@ -722,13 +722,12 @@ int gh_file_info(void* h, int64_t* slots, int32_t* shards, int64_t* held);
  * quirk pre-pass where it applies (0 the two-sweep one); JOBS_FLAT 1 lane
  * jobs dealt one per lane (0 by region); RMV_FULL7 1 the full-grid REMOVE
  * launch without a block loop; DNW / NREC 1 the nibble path's move words /
- * row records are kept (0 also where they do not apply: shards); SIDE 0 / 1 /
- * 2 side streams of the idle round variants, SIDE_ORDER their order,
- * JOIN_STAMP how they join; FORCE_SLOW / FORCE_STORM every segment by the
+ * row records are kept (0 also where they do not apply: shards);
+ * FORCE_SLOW / FORCE_STORM every segment by the
  * per-cell rule / the storm variant every round; ROUND_NT, ROUND_TPW,
  * ROUND_XMAP k_round's non-temporal streams, tiles per workgroup and tile
- * map; SLOW_GRID workgroups of the per-cell kernel; NIB_RMV, NIB_DMA REMOVE
- * on / LDS-DMA staging of the nibble path; GX_DIRECT same-device row shards
+ * map; SLOW_GRID workgroups of the per-cell kernel; NIB_RMV REMOVE
+ * on the nibble path; GX_DIRECT same-device row shards
  * gather their ghosts' planes in place; TMODE the timing mode; PLANE, C8 the
  * sender plane and the 4-bit tier are kept; TILE_W the members per table tile
  * this engine (or shard) runs with: gh_config.tile_width, or its default with
@@ -736,9 +735,8 @@ int gh_file_info(void* h, int64_t* slots, int32_t* shards, int64_t* held);
  * min(n_out, GH_KNOB_COUNT) values; *count (may be NULL) = GH_KNOB_COUNT. No
  * reference counterpart. */
 enum {
-  GH_KNOB_QUIRK_ROWS = 0, GH_KNOB_JOBS_FLAT, GH_KNOB_RMV_FULL7, GH_KNOB_DNW, GH_KNOB_NREC, GH_KNOB_SIDE,
-  GH_KNOB_SIDE_ORDER, GH_KNOB_JOIN_STAMP, GH_KNOB_FORCE_SLOW, GH_KNOB_FORCE_STORM, GH_KNOB_ROUND_NT,
-  GH_KNOB_ROUND_TPW, GH_KNOB_SLOW_GRID, GH_KNOB_NIB_RMV, GH_KNOB_NIB_DMA, GH_KNOB_GX_DIRECT,
+  GH_KNOB_QUIRK_ROWS = 0, GH_KNOB_JOBS_FLAT, GH_KNOB_RMV_FULL7, GH_KNOB_DNW, GH_KNOB_NREC, GH_KNOB_FORCE_SLOW,
+  GH_KNOB_FORCE_STORM, GH_KNOB_ROUND_NT, GH_KNOB_ROUND_TPW, GH_KNOB_SLOW_GRID, GH_KNOB_NIB_RMV, GH_KNOB_GX_DIRECT,
   GH_KNOB_ROUND_XMAP, GH_KNOB_TMODE, GH_KNOB_PLANE, GH_KNOB_C8, GH_KNOB_TILE_W, GH_KNOB_COUNT
 };
 int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count);

@@ -938,7 +938,8 @@ struct GhRound {
   int32_t force_slow;   // diagnostics (GH_FORCE_SLOW): every segment by the per-cell rule
   int32_t nib_rmv;      // nibble path: REMOVE'd members with >= 2 detectors stay on it (GH_NIB_RMV=0: lane jobs;
                         // 2: k_round IN 6 every round, else only in rounds with a detection)
-  int32_t nib_dma;      // nibble path: LDS-DMA staging of the own and sender lines (GH_NIB_DMA; column layout, TW 256)
+  int32_t spare;        // unused (the retired LDS-DMA switch's word): keeps the offsets below, which k_round's
+                        // scalar loads and, through its SGPR spills, the storm variant's scratch follow
   int32_t shadow_row;   // the introducer while it may hold D7 shadow entries (its segments take k_round_slow), else -1
   int32_t vslot;        // the round's index in its gh_step call (vlog: which k_round variant ran)
   int32_t rmv_full;     // k_round IN 6 on a full grid: the host knows a REMOVE is pending this round

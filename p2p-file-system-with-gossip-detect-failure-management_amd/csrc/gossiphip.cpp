@@ -43,8 +43,8 @@ struct Engine {
   // on a side stream (forked after the round's inputs, joined before the lane
   // jobs): one of the four runs, the three idle ones return at once while the
   // nibble path runs, off the round's critical path
-  hipStream_t vstream = nullptr, vstream2 = nullptr;
-  hipEvent_t vfork = nullptr, vjoin = nullptr, vjoin2 = nullptr;
+  hipStream_t vstream = nullptr;
+  hipEvent_t vjoin = nullptr;  // the join when the side stream's last launch does not happen
   hipEvent_t vstart = nullptr;  // the nibble launch's start stamp when not timing (the side stream's fork)
   hipEvent_t vstop = nullptr;   // the last idle launch's end stamp when not timing (the join)
   GhDev d{};
@@ -62,10 +62,8 @@ struct Engine {
   int force_slow = 0;    // every segment by the per-cell rule (GH_FORCE_SLOW, diagnostics)
   int nib_rmv = 1;       // REMOVE'd members with >= 2 detectors on the nibble path (GH_NIB_RMV=0: lane jobs,
                          // 2: the REMOVE-taking instantiation every round; A/B)
-  int nib_dma = 0;       // the nibble path stages its lines by LDS-DMA (GH_NIB_DMA=1, A/B)
   bool shadow_any = false;  // the introducer's row may hold D7 shadow entries (GhDev.shadow; re-read after each gh_step)
   bool timing = false;
-  int side = 1;          // idle round variants on the side stream (GH_SIDE=0: in line; 2: two side streams)
   // the current table may hold flags no round kernel counted (import, fill,
   // events, list merges): the next quirk pre-pass runs ungated
   bool qforce = true;
@@ -128,11 +126,9 @@ struct Engine {
   // events around them, and the device logs which variant ran (vlog).
   // tmode 0: every variant launch carries its own events.
   int tmode = 1;
-  int join_stamp = 1;  // GH_JOIN_STAMP=0: the join as an event recorded after the side stream's last launch (A/B)
   int quirk_rows = 1;  // GH_QUIRK_ROWS=0: the two-sweep quirk pre-pass where the one-pass row walk applies (A/B)
   int gx_direct = 1;  // GH_GX_DIRECT=0: same-device in-process row shards pack and copy their ghosts' planes (A/B)
   GxPeers gx_pub{};   // what this shard publishes for the direct gather (entry 0)
-  int side_order = 0;  // GH_SIDE_ORDER=1: the side stream's idle variants as IN 1, IN 3, storm, IN 6 (A/B)
   // read by gh_create like the switches above, so that an engine created
   // after the variable changed gets the new value (gh_debug_knobs reports them)
   int jobs_flat = 1;   // GH_JOBS_FLAT=0: the region-form k_round_jobs (A/B)
@@ -270,7 +266,6 @@ GhRound round_params(const Engine* e, int32_t r) {
   p.force_storm = e->force_storm;
   p.force_slow = e->force_slow;
   p.nib_rmv = e->nib_rmv;
-  p.nib_dma = e->nib_dma;
   p.rmv_full7 = e->rmv_full7;
   p.jobs_flat = e->jobs_flat;
   p.slow_grid = e->slow_grid;
@@ -1192,7 +1187,6 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   if (const char* v = std::getenv("GH_FORCE_STORM")) e->force_storm = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_FORCE_SLOW")) e->force_slow = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_NIB_RMV")) e->nib_rmv = std::min(2, std::max(0, std::atoi(v)));
-  if (const char* v = std::getenv("GH_NIB_DMA")) e->nib_dma = std::atoi(v) != 0;
   if (tw != 8 && tw != 16 && tw != 32 && tw != 64 && tw != 128 && tw != 256) {
     delete e;
     return GH_EINVAL;
@@ -1202,10 +1196,7 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   // half of it the plane itself (its window is the plane's: lags of healthy
   // pull dissemination); the row layout ships 16-bit ghost rows
   e->c8 = e->plane && e->tpw == 1 && tw >= 64;
-  if (const char* v = std::getenv("GH_SIDE")) e->side = std::min(2, std::max(0, std::atoi(v)));
   if (const char* v = std::getenv("GH_TMODE")) e->tmode = std::atoi(v) != 0;
-  if (const char* v = std::getenv("GH_SIDE_ORDER")) e->side_order = std::atoi(v) != 0;
-  if (const char* v = std::getenv("GH_JOIN_STAMP")) e->join_stamp = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_QUIRK_ROWS")) e->quirk_rows = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_GX_DIRECT")) e->gx_direct = std::atoi(v) != 0;
   if (const char* v = std::getenv("GH_C8")) e->c8 = e->c8 && std::atoi(v) != 0;
@@ -1265,10 +1256,7 @@ int create(const gh_config* cfg, int32_t rank, int32_t world, int32_t transport,
   if (!dry) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   if (!dry && (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
                hipStreamCreateWithPriority(&e->vstream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-               hipStreamCreateWithPriority(&e->vstream2, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-               hipEventCreateWithFlags(&e->vfork, hipEventDisableTiming) != hipSuccess ||
                hipEventCreateWithFlags(&e->vjoin, hipEventDisableTiming) != hipSuccess ||
-               hipEventCreateWithFlags(&e->vjoin2, hipEventDisableTiming) != hipSuccess ||
                hipEventCreate(&e->vstart) != hipSuccess || hipEventCreate(&e->vstop) != hipSuccess)) {
     gh_destroy(e);  // the streams and events created before the failing one, and the communicator
     return GH_EHIP;
@@ -1570,6 +1558,155 @@ int build_inboxes(Engine* e, const GhRound& p) {
   return GH_OK;
 }
 
+// Whether round r would overflow a running member's heartbeat (*hit), asked
+// once the bound of the table's heartbeats has reached INT32_MAX.
+int hb_overflow(Engine* e, int32_t r, int32_t* hit) {
+  // a heartbeat may sit at INT32_MAX: the round would overflow Go's
+  // HeartbeatCount (slave/slave.go:446) in our int32; refused (SPEC §2)
+  // before its events are applied, so they stay pending. The rows that
+  // run it: alive and not crashing or leaving in its events (und is the
+  // round's scratch, rewritten by decide_active)
+  std::vector<uint8_t> runs(e->alive.begin(), e->alive.end());
+  for (const auto& x : e->pending)
+    if (x.kind == GH_EV_CRASH || x.kind == GH_EV_LEAVE) runs[x.member] = 0;
+  HIPCHK(e, hipMemcpyAsync(e->d.und, runs.data(), e->n, hipMemcpyHostToDevice, e->stream));
+  int32_t* flag = e->d.wn + 2;
+  *hit = 0;
+  HIPCHK(e, hipMemsetAsync(flag, 0, sizeof(int32_t), e->stream));
+  launch_hb_check(e->d, e->cur, flag, round_params(e, r), e->stream);
+  HIPCHK(e, hipGetLastError());
+  COMMCHK(e, e->comm->allreduce(flag, flag, 1, GH_DT_I32, GH_OP_MAX, e->stream));
+  HIPCHK(e, hipMemcpyAsync(hit, flag, sizeof *hit, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return GH_OK;
+}
+
+// The variants of k_round for round slot pr.vslot of a call; the ones not
+// selected return at once. tsel: timing the nibble launch alone (the others
+// bracketed, the variant that ran logged); *mvq is then the variant the
+// nibble launch was.
+int launch_variants(Engine* e, const GhRound& pr, bool tsel, int8_t* mvq) {
+  const int32_t q = pr.vslot;
+  // With timing on, a launch stamps its own start and end (events 12q + 2v,
+  // 12q + 2v + 1 of variant v; hipExtLaunchKernel, no event packets between
+  // the kernels): every launch, or (tsel) the nibble path's, and the other
+  // variants together, from the start of the first (v0) to the end of the
+  // last (v4) (events 12q + 10, 12q + 11), as a stamped launch costs its
+  // stream ~5 us
+  // The nibble launch: IN 2 (variant 3), or IN 6 (variant 4, on a full
+  // grid) when the host knows a REMOVE is pending (the first round of a
+  // call after a detection, one engine, the tier's default modes): IN 2
+  // cannot be the one selected then, so it is not launched, and the
+  // REMOVE round's nibble path runs on the round's stream
+  const bool rmv_main = e->c8 && pr.rmv_full && !e->rowlay && e->nib_rmv >= 1 && (!e->timing || tsel);
+  const int mv = rmv_main ? 4 : 3;
+  if (tsel) *mvq = (int8_t)mv;
+  const int nside = rmv_main ? 3 : 4;
+  // the idle variants, the first nside of them (side stream: the first one
+  // is dispatched between the nibble path's workgroups, the rest after it)
+  static constexpr int sides[4] = {0, 1, 2, 4};
+  auto ev = [&](int v, int end) -> hipEvent_t {
+    if (!e->timing) return nullptr;
+    if (!tsel) return e->evs[12 * q + 2 * v + end];
+    if (v == mv) return e->evs[12 * q + 6 + end];
+    if (v == sides[0] && end == 0) return e->evs[12 * q + 10];
+    if (v == sides[nside - 1] && end == 1) return e->evs[12 * q + 11];
+    return nullptr;
+  };
+  if (!e->c8) {  // lean 16-bit input, storm
+    for (int v = 0; v < 2; ++v) launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, v, ev(v, 0), ev(v, 1));
+    return GH_OK;
+  }
+  // lean 16-bit input, storm, lean tier input by the 16-bit rule and the
+  // REMOVE-taking nibble path on the side stream, beside the nibble
+  // launch
+  // (forked at the nibble launch's own start stamp: its stream's earlier
+  // work, the inboxes, is done then; an event packet of its own before
+  // it had cost the round ~10 us)
+  hipEvent_t st = e->timing ? ev(mv, 0) : e->vstart;
+  launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, mv, st, ev(mv, 1));
+  HIPCHK(e, hipStreamWaitEvent(e->vstream, st, 0));
+  // joined at the last idle launch's own end stamp (as the fork uses the
+  // nibble launch's start stamp), not at an event packet after it
+  // (a last launch that did not happen, e.g. IN 6 on row shards: an event
+  // packet after the others)
+  hipEvent_t jn = nullptr;
+  for (int x = 0; x < nside; ++x) {
+    hipEvent_t t1 = ev(sides[x], 1);
+    const bool last = x == nside - 1;
+    if (last && !t1) t1 = e->vstop;
+    if (launch_round(e->d, e->cur, e->dcur, pr, e->vstream, e->nt, sides[x], ev(sides[x], 0), t1) && last) jn = t1;
+  }
+  if (!jn) {
+    HIPCHK(e, hipEventRecord(e->vjoin, e->vstream));
+    jn = e->vjoin;
+  }
+  HIPCHK(e, hipStreamWaitEvent(e->stream, jn, 0));
+  return GH_OK;
+}
+
+// Row shards: every shard detected in its own rows: D_r's counts and first
+// detectors over all of them (MIN as the MAX of negations).
+int reduce_detections(Engine* e) {
+  int rc;
+  int32_t* dc = e->d.det_cnt[e->dcur ^ 1];
+  int32_t* dm = e->d.det_min[e->dcur ^ 1];
+  if ((rc = allreduce_i32(e, dc, dc, e->ld))) return rc;
+  launch_negate(dm, e->ld, e->stream);
+  COMMCHK(e, e->comm->allreduce(dm, dm, e->ld, GH_DT_I32, GH_OP_MAX, e->stream));
+  launch_negate(dm, e->ld, e->stream);
+  HIPCHK(e, hipGetLastError());
+  return GH_OK;
+}
+
+// D_r replaces D_{r-1} (k_finish), between the two halves of the
+// reference's REMOVE recipients of D_r: the sweep's column bitmaps
+// (needs D_{r-1}, before k_finish replaces it), then per member of D_r
+// (an armed engine, gh_set_partition: the detectors' bitmaps alone, then
+// rule D4 per side)
+int finish_round(Engine* e, const GhRound& p) {
+  if (e->rm_ref) launch_rm_cols(e->d, e->cur, e->dcur, p, e->stream);
+  if (e->part) launch_part_cols(e->d, e->cur, e->dcur, p, e->stream);
+  launch_finish(e->d, e->dcur, p, e->stream);
+  if (e->rm_ref) launch_rm_recv(e->d, e->dcur ^ 1, p, e->stream);
+  if (e->part) {
+    if (e->d.ctl && (e->ctl_kinds & GH_CTL_REMOVE))  // lossy REMOVEs: per message (SPEC §2 step 6c)
+      launch_ctl_recv(e->d, e->dcur ^ 1, p, e->one_side, e->stream);
+    else
+      launch_part_recv(e->d, e->dcur ^ 1, p, e->stream);
+  }
+  HIPCHK(e, hipGetLastError());
+  return GH_OK;
+}
+
+// gh_set_timing: adds the k_round time of a call's done rounds, each round
+// that of the variant that ran (mvlog: launch_variants' *mvq per round).
+int read_timing(Engine* e, bool tsel, int32_t done, const std::vector<int8_t>& mvlog) {
+  std::vector<int32_t> vl;
+  if (tsel && done > 0) {
+    vl.resize(done);
+    // (on the engine's stream: a first use of the null stream costs ms)
+    HIPCHK(e, hipMemcpyAsync(vl.data(), e->vlog, sizeof(int32_t) * done, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  }
+  for (int32_t q = 0; q < done; ++q) {
+    float ms = 0.f;  // the variant that ran
+    if (tsel) {
+      const int b = vl[q] == mvlog[q] ? 12 * q + 6 : 12 * q + 10;
+      HIPCHK(e, hipEventElapsedTime(&ms, e->evs[b], e->evs[b + 1]));
+    }
+    for (int v = 0; !tsel && v < (e->c8 ? 5 : 2); ++v) {
+      float mv = 0.f;
+      const int b = 12 * q + 2 * v;
+      HIPCHK(e, hipEventElapsedTime(&mv, e->evs[b], e->evs[b + 1]));
+      ms = std::max(ms, mv);
+    }
+    e->timed_ms += ms;
+    e->timed_launches++;
+  }
+  return GH_OK;
+}
+
 // Runs an encoding launch (pack / fill) of buffer cur until it fits the wide
 // arena: on overflow the arena grows and the launch repeats (both are
 // idempotent rewrites of whole rows).
@@ -1780,10 +1917,7 @@ void gh_destroy(void* h) {
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   if (e->vstream) (void)hipStreamDestroy(e->vstream);
-  if (e->vstream2) (void)hipStreamDestroy(e->vstream2);
-  if (e->vfork) (void)hipEventDestroy(e->vfork);
   if (e->vjoin) (void)hipEventDestroy(e->vjoin);
-  if (e->vjoin2) (void)hipEventDestroy(e->vjoin2);
   if (e->vstart) (void)hipEventDestroy(e->vstart);
   if (e->vstop) (void)hipEventDestroy(e->vstop);
   delete e;
@@ -2080,7 +2214,7 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     }
   }
   // timing the nibble launch alone (the others bracketed, the variant that ran logged)
-  const bool tsel = e->timing && e->tmode == 1 && e->c8 && e->side != 2;
+  const bool tsel = e->timing && e->tmode == 1 && e->c8;
   if (tsel && e->vlog_cap < rounds) {  // (gh_set_timing allocates 4,096 rounds' worth)
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->vlog) HIPCHK(e, hipFree(e->vlog));
@@ -2098,29 +2232,14 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     const int32_t r = e->round + 1;
     int rc;
     if (e->hb_bound >= INT32_MAX) {
-      // a heartbeat may sit at INT32_MAX: the round would overflow Go's
-      // HeartbeatCount (slave/slave.go:446) in our int32; refused (SPEC §2)
-      // before its events are applied, so they stay pending. The rows that
-      // run it: alive and not crashing or leaving in its events (und is the
-      // round's scratch, rewritten by decide_active)
-      std::vector<uint8_t> runs(e->alive.begin(), e->alive.end());
-      for (const auto& x : e->pending)
-        if (x.kind == GH_EV_CRASH || x.kind == GH_EV_LEAVE) runs[x.member] = 0;
-      HIPCHK(e, hipMemcpyAsync(e->d.und, runs.data(), e->n, hipMemcpyHostToDevice, e->stream));
-      int32_t* flag = e->d.wn + 2;
       int32_t hit = 0;
-      HIPCHK(e, hipMemsetAsync(flag, 0, sizeof(int32_t), e->stream));
-      launch_hb_check(e->d, e->cur, flag, round_params(e, r), e->stream);
-      HIPCHK(e, hipGetLastError());
-      COMMCHK(e, e->comm->allreduce(flag, flag, 1, GH_DT_I32, GH_OP_MAX, e->stream));
-      HIPCHK(e, hipMemcpyAsync(&hit, flag, sizeof hit, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
+      if ((rc = hb_overflow(e, r, &hit))) return rc;
       if (hit) {
         status = set_err(e, GH_ERANGE, "a running member's heartbeat is INT32_MAX: the round would overflow it");
         break;
       }
     }
-    if ((rc = process_events(e, r))) return rc;
+    if ((rc = process_events(e, r))) return rc;  // step 0
     if (e->pforce) {  // the table was rewritten outside a round: no valid plane
       HIPCHK(e, hipMemsetAsync(e->d.pvalid + e->cur, 0, sizeof(int32_t), e->stream));
       e->pforce = false;
@@ -2136,7 +2255,7 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     if (e->rowlay && e->world > 1)  // each column's base from its owner row's shard
       COMMCHK(e, e->comm->allreduce(e->d.base[e->cur ^ 1], e->d.base[e->cur ^ 1], e->ld, GH_DT_I32, GH_OP_MAX,
                                     e->stream));
-    if ((rc = decide_active(e, p))) return rc;
+    if ((rc = decide_active(e, p))) return rc;  // step 2
     if (e->cfg.detect_mode == GH_DETECT_QUIRK) {
       // skip the pre-pass when no shard's table holds a flag (the round
       // kernels count flagged segments as they write; the counts are summed
@@ -2158,121 +2277,20 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
     pr.vslot = q;
     // (GH_NIB_RMV=0, the other leg of that A/B: no REMOVE on the nibble path, so no IN 6 / IN 7)
     pr.rmv_full = q == 0 && e->world == 1 && last_nd > 0 && e->nib_rmv >= 1;
-    // the variants of k_round; the ones not selected return at once. With
-    // timing on, a launch stamps its own start and end (events 12q + 2v,
-    // 12q + 2v + 1 of variant v; hipExtLaunchKernel, no event packets between
-    // the kernels): every launch, or (tsel) the nibble path's, and the other
-    // variants together, from the start of the first (v0) to the end of the
-    // last (v4) (events 12q + 10, 12q + 11), as a stamped launch costs its
-    // stream ~5 us
-    // The nibble launch: IN 2 (variant 3), or IN 6 (variant 4, on a full
-    // grid) when the host knows a REMOVE is pending (the first round of a
-    // call after a detection, one engine, the tier's default modes): IN 2
-    // cannot be the one selected then, so it is not launched, and the
-    // REMOVE round's nibble path runs on the round's stream
-    const bool rmv_main = e->c8 && pr.rmv_full && !e->rowlay && e->nib_rmv >= 1 && !e->nib_dma &&
-                          (!e->timing || tsel);
-    const int mv = rmv_main ? 4 : 3;
-    if (e->timing && tsel) mvlog[q] = (int8_t)mv;
-    const int nside = rmv_main ? 3 : 4;
-    // the idle variants, the first nside of them (side stream: the first one
-    // is dispatched between the nibble path's workgroups, the rest after it)
-    int sides[4] = {0, 1, 2, 4};
-    if (e->side_order) {
-      sides[0] = 2, sides[1] = 0, sides[2] = 1;
-    }
-    auto ev = [&](int v, int end) -> hipEvent_t {
-      if (!e->timing) return nullptr;
-      if (!tsel) return e->evs[12 * q + 2 * v + end];
-      if (v == mv) return e->evs[12 * q + 6 + end];
-      if (v == sides[0] && end == 0) return e->evs[12 * q + 10];
-      if (v == sides[nside - 1] && end == 1) return e->evs[12 * q + 11];
-      return nullptr;
-    };
-    if (e->c8 && !e->side) {
-      // lean 16-bit input, storm, lean tier input by the 16-bit rule, the
-      // nibble path that takes REMOVE deliveries, then the steady nibble
-      // path, all on the round's stream
-      for (int x = 0; x < nside; ++x)
-        launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, sides[x], ev(sides[x], 0), ev(sides[x], 1));
-      launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, mv, ev(mv, 0), ev(mv, 1));
-    } else if (e->c8 && e->side == 2) {
-      // the same on two side streams, so that after the nibble path only one
-      // idle launch per stream is left to run (the first on each spans it)
-      HIPCHK(e, hipEventRecord(e->vfork, e->stream));
-      HIPCHK(e, hipStreamWaitEvent(e->vstream, e->vfork, 0));
-      HIPCHK(e, hipStreamWaitEvent(e->vstream2, e->vfork, 0));
-      for (int v : {0, 1}) launch_round(e->d, e->cur, e->dcur, pr, e->vstream, e->nt, v, ev(v, 0), ev(v, 1));
-      for (int v : {4, 2}) launch_round(e->d, e->cur, e->dcur, pr, e->vstream2, e->nt, v, ev(v, 0), ev(v, 1));
-      HIPCHK(e, hipEventRecord(e->vjoin, e->vstream));
-      HIPCHK(e, hipEventRecord(e->vjoin2, e->vstream2));
-      launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, 3, ev(3, 0), ev(3, 1));
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->vjoin, 0));
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->vjoin2, 0));
-    } else if (e->c8) {
-      // lean 16-bit input, storm, lean tier input by the 16-bit rule and the
-      // REMOVE-taking nibble path on the side stream, beside the nibble
-      // launch
-      // (forked at the nibble launch's own start stamp: its stream's earlier
-      // work, the inboxes, is done then; an event packet of its own before
-      // it had cost the round ~10 us)
-      hipEvent_t st = e->timing ? ev(mv, 0) : e->vstart;
-      launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, mv, st, ev(mv, 1));
-      HIPCHK(e, hipStreamWaitEvent(e->vstream, st, 0));
-      // joined at the last idle launch's own end stamp (as the fork uses the
-      // nibble launch's start stamp), not at an event packet after it
-      // (a last launch that did not happen, e.g. IN 6 on row shards: an event
-      // packet after the others)
-      hipEvent_t jn = nullptr;
-      for (int x = 0; x < nside; ++x) {
-        hipEvent_t t1 = ev(sides[x], 1);
-        const bool last = x == nside - 1 && e->join_stamp;
-        if (last && !t1) t1 = e->vstop;
-        if (launch_round(e->d, e->cur, e->dcur, pr, e->vstream, e->nt, sides[x], ev(sides[x], 0), t1) && last) jn = t1;
-      }
-      if (!jn) {
-        HIPCHK(e, hipEventRecord(e->vjoin, e->vstream));
-        jn = e->vjoin;
-      }
-      HIPCHK(e, hipStreamWaitEvent(e->stream, jn, 0));
-    } else {  // lean 16-bit input, storm
-      for (int v = 0; v < 2; ++v) launch_round(e->d, e->cur, e->dcur, pr, e->stream, e->nt, v, ev(v, 0), ev(v, 1));
-    }
+    // steps 1 to 6 as one pass over the table (SPEC §3): the k_round
+    // variants, then the lane jobs and the per-cell rule for what they left
+    if ((rc = launch_variants(e, pr, tsel, tsel ? &mvlog[q] : nullptr))) return rc;
     // (row layout: the ghosts' codes before the kernels that may read them)
     if ((rc = ghost_codes_if_slow(e))) return rc;
     launch_round_jobs(e->d, e->cur, e->dcur, pr, e->stream);
     launch_round_slow(e->d, e->cur, e->dcur, pr, e->stream);
-    if (e->rowlay && e->world > 1) {
-      // every shard detected in its own rows: D_r's counts and first
-      // detectors over all of them (MIN as the MAX of negations)
-      int32_t* dc = e->d.det_cnt[e->dcur ^ 1];
-      int32_t* dm = e->d.det_min[e->dcur ^ 1];
-      if ((rc = allreduce_i32(e, dc, dc, e->ld))) return rc;
-      launch_negate(dm, e->ld, e->stream);
-      COMMCHK(e, e->comm->allreduce(dm, dm, e->ld, GH_DT_I32, GH_OP_MAX, e->stream));
-      launch_negate(dm, e->ld, e->stream);
-      HIPCHK(e, hipGetLastError());
-    }
+    if (e->rowlay && e->world > 1 && (rc = reduce_detections(e))) return rc;
     if (e->lorder) {  // the lists of the next state (needs D_{r-1} and the inboxes)
       launch_list_round(e->d, e->cur, e->dcur, p, e->lcur, e->stream);
       e->lcur ^= 1;
       if ((rc = list_sync(e, e->lcur))) return rc;
     }
-    // the reference's REMOVE recipients of D_r: the sweep's column bitmaps
-    // (needs D_{r-1}, before k_finish replaces it), then per member of D_r
-    // (an armed engine, gh_set_partition: the detectors' bitmaps alone, then
-    // rule D4 per side)
-    if (e->rm_ref) launch_rm_cols(e->d, e->cur, e->dcur, p, e->stream);
-    if (e->part) launch_part_cols(e->d, e->cur, e->dcur, p, e->stream);
-    launch_finish(e->d, e->dcur, p, e->stream);
-    if (e->rm_ref) launch_rm_recv(e->d, e->dcur ^ 1, p, e->stream);
-    if (e->part) {
-      if (e->d.ctl && (e->ctl_kinds & GH_CTL_REMOVE))  // lossy REMOVEs: per message (SPEC §2 step 6c)
-        launch_ctl_recv(e->d, e->dcur ^ 1, p, e->one_side, e->stream);
-      else
-        launch_part_recv(e->d, e->dcur ^ 1, p, e->stream);
-    }
-    HIPCHK(e, hipGetLastError());
+    if ((rc = finish_round(e, p))) return rc;
     e->cur ^= 1;
     e->dcur ^= 1;
     e->round = r;
@@ -2319,30 +2337,7 @@ int gh_step(void* h, int32_t rounds, gh_round_stats* stats) {
       return set_err(e, err, "device error in a round");
     }
   }
-  if (e->timing) {
-    std::vector<int32_t> vl;
-    if (tsel && done > 0) {
-      vl.resize(done);
-      // (on the engine's stream: a first use of the null stream costs ms)
-      HIPCHK(e, hipMemcpyAsync(vl.data(), e->vlog, sizeof(int32_t) * done, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-    }
-    for (int32_t q = 0; q < done; ++q) {
-      float ms = 0.f;  // the variant that ran
-      if (tsel) {
-        const int b = vl[q] == mvlog[q] ? 12 * q + 6 : 12 * q + 10;
-        HIPCHK(e, hipEventElapsedTime(&ms, e->evs[b], e->evs[b + 1]));
-      }
-      for (int v = 0; !tsel && v < (e->c8 ? 5 : 2); ++v) {
-        float mv = 0.f;
-        const int b = 12 * q + 2 * v;
-        HIPCHK(e, hipEventElapsedTime(&mv, e->evs[b], e->evs[b + 1]));
-        ms = std::max(ms, mv);
-      }
-      e->timed_ms += ms;
-      e->timed_launches++;
-    }
-  }
+  if (e->timing && (rc0 = read_timing(e, tsel, done, mvlog))) return rc0;
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
     stats->rounds = done;
@@ -3574,16 +3569,12 @@ int gh_debug_knobs(void* h, int32_t* out, int64_t n_out, int64_t* count) {
   v[GH_KNOB_RMV_FULL7] = e->rmv_full7;
   v[GH_KNOB_DNW] = e->d.dnw != nullptr;  // (in effect: the buffers exist only where the switch applies)
   v[GH_KNOB_NREC] = e->d.nmeta != nullptr;
-  v[GH_KNOB_SIDE] = e->side;
-  v[GH_KNOB_SIDE_ORDER] = e->side_order;
-  v[GH_KNOB_JOIN_STAMP] = e->join_stamp;
   v[GH_KNOB_FORCE_SLOW] = e->force_slow;
   v[GH_KNOB_FORCE_STORM] = e->force_storm;
   v[GH_KNOB_ROUND_NT] = e->nt;
   v[GH_KNOB_ROUND_TPW] = e->tpw;
   v[GH_KNOB_SLOW_GRID] = e->slow_grid;
   v[GH_KNOB_NIB_RMV] = e->nib_rmv;
-  v[GH_KNOB_NIB_DMA] = e->nib_dma;
   v[GH_KNOB_GX_DIRECT] = e->gx_direct;
   v[GH_KNOB_ROUND_XMAP] = e->xmap;
   v[GH_KNOB_TMODE] = e->tmode;

@@ -1067,13 +1067,9 @@ __device__ __forceinline__ void nib_word(bool tt, uint32_t qw, uint32_t aw, uint
 // plane segment in the tile slice, as with columns) or a ghost row whose
 // plane words the round's exchange put in the ghost table (row-major,
 // gplane); the gathers then take per-sender 64-bit addresses staged in LDS.
-// DMA (one engine or column shards, 16 cells per lane): each wave stages its
-// 8 rows of a step into its own LDS region by LDS-DMA (buffer_load_dwordx4
-// ... lds, 16 B per lane: the own lag and age lines as two 1-KiB pieces, the
-// 32 sender lines as four), then computes them on ds_read_b64 in the 16-cell
-// lane shape: half the vector-memory load instructions of 8-B register loads,
-// and no VGPRs held by loads in flight.
-// SPL (16-cell lanes, 256-member tiles; not with DMA): lanes
+// (Staging a wave's own and sender lines into LDS by LDS-DMA instead of
+// register loads measured slower and is gone: DESIGN.md.)
+// SPL (16-cell lanes, 256-member tiles): lanes
 // m and m + 8 of a row's 16 share 32 cells; lane m gathers 16 B of those
 // cells from senders 0 and 1, lane m + 8 from senders 2 and 3 (2 gathers of
 // 16 B per row step instead of 4 of 8 B: each wave instruction then touches 8
@@ -1088,7 +1084,7 @@ __device__ __forceinline__ void nib_word(bool tt, uint32_t qw, uint32_t aw, uint
 // RMV); the other one (the steady state's: 10 VGPRs fewer, 7 waves per SIMD
 // instead of 6) hands every lane holding a REMOVE'd member to the lane jobs.
 // k_round runs the RMV one only in rounds with a pending REMOVE (IN 6).
-template <int TW, bool NT, int CPL, bool ROWS, bool DMA = false, bool RMVK = true>
+template <int TW, bool NT, int CPL, bool ROWS, bool RMVK = true>
 __device__ __forceinline__ void round_block_nib(const GhDev& d, const int cur, const int dcur, const GhRound& p,
                                                 const int bid) {
   constexpr int W = CPL / 8;         // dwords per lane and plane
@@ -1100,12 +1096,7 @@ __device__ __forceinline__ void round_block_nib(const GhDev& d, const int cur, c
   constexpr int RS = GH_NIB_RS > 0 ? GH_NIB_RS : (CPL <= 16 ? 2 : 1);  // row steps per iteration
   static_assert(SEG >= 2 && SEG <= 64 && RB % (RSTEP * RS) == 0, "nibble path: whole row steps");
   static_assert(W == 2 || W == 4, "nibble path: 16 or 32 cells per lane (one or two lane jobs of 16 cells)");
-  static_assert(!DMA || (!ROWS && CPL == 16 && TW == 256 && RB % 32 == 0), "LDS-DMA staging: 16-cell lanes, 256-member tiles");
-  constexpr int RSD = DMA ? 2 : RS;  // row steps per iteration (DMA: a wave's 8 consecutive rows)
-  constexpr bool SPL = (ROWS ? GH_NIB_SPLIT_ROWS : GH_NIB_SPLIT) && !DMA && CPL == 16 && TW == 256;
-  // per wave: own lag 1 KiB, age 1 KiB, the 4 gather pieces (sender slot q
-  // of the 8 rows) 1 KiB each
-  __shared__ __attribute__((aligned(16))) uint32_t s_dma[DMA ? 4 * 1536 : 1];
+  constexpr bool SPL = (ROWS ? GH_NIB_SPLIT_ROWS : GH_NIB_SPLIT) && CPL == 16 && TW == 256;
   constexpr int H = W / 2;  // lane jobs of GH_JOB_CPL cells per job lane
   __shared__ unsigned long long s_merged, s_rel, s_tmb;
   __shared__ int s_quiet, s_nslow, s_slowbase, s_bmove, s_hasjob;
@@ -1275,39 +1266,14 @@ __device__ __forceinline__ void round_block_nib(const GhDev& d, const int cur, c
   uint32_t n_mrg = 0, n_rel = 0, n_tmb = 0;
 
 #pragma unroll 1
-  for (int it = 0; it < RB / RSTEP; it += RSD) {
-    int iu[RSD];
-    bool alu[RSD], oku[RSD];
-    uint32_t owu[RSD];
-    NibWords<W> awu[RSD], qwu[RSD], pwu[RSD][4];
-    char* wb = reinterpret_cast<char*>(s_dma) + (DMA ? wave * 6144 : 0);
-    if constexpr (DMA) {
-      // the wave's rows it * RSTEP + wave * 8 .. + 7 of the block: their own
-      // lines are one contiguous KiB of each plane's tile slice; DMA lane l
-      // moves bytes [16 l, 16 l + 16), and for sender slot q the 16 B at
-      // (l % 8) * 16 of row l / 8's sender line (hipcc does not wait for an
-      // LDS-DMA: the waits are explicit)
-      typedef __attribute__((address_space(3))) void lds_t;
-      const int rbase = it * RSTEP + wave * 8;
-      const uint32_t own = (uint32_t)(rb * RB + rbase) * (TW / 2) + (uint32_t)lane * 16u;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous step's LDS reads are done
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(plo_t, (lds_t*)wb, 16, (int)own, 0, 0, GH_NIB_OWN_AUX);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a4o_t, (lds_t*)(wb + 1024), 16, (int)own, 0, 0, GH_NIB_AGE_AUX);
-      const int4 sv4 = *reinterpret_cast<const int4*>(&s_inb[(rbase + (lane >> 3)) * KB]);
-      const uint32_t dcol = (uint32_t)(lane & 7) * 16u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(plo_t, (lds_t*)(wb + 2048), 16, (int)((uint32_t)sv4.x + dcol), 0, 0,
-                                               GH_NIB_GAT_AUX);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(plo_t, (lds_t*)(wb + 3072), 16, (int)((uint32_t)sv4.y + dcol), 0, 0,
-                                               GH_NIB_GAT_AUX);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(plo_t, (lds_t*)(wb + 4096), 16, (int)((uint32_t)sv4.z + dcol), 0, 0,
-                                               GH_NIB_GAT_AUX);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(plo_t, (lds_t*)(wb + 5120), 16, (int)((uint32_t)sv4.w + dcol), 0, 0,
-                                               GH_NIB_GAT_AUX);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+  for (int it = 0; it < RB / RSTEP; it += RS) {
+    int iu[RS];
+    bool alu[RS], oku[RS];
+    uint32_t owu[RS];
+    NibWords<W> awu[RS], qwu[RS], pwu[RS][4];
 #pragma unroll
-    for (int u = 0; u < RSD; ++u) {
-      const int rr = DMA ? it * RSTEP + wave * 8 + u * RPW + sub : wave * RPW + (it + u) * RSTEP + sub;
+    for (int u = 0; u < RS; ++u) {
+      const int rr = wave * RPW + (it + u) * RSTEP + sub;
       const int i_raw = (int)d.row0 + rb * RB + rr;
       const bool valid = i_raw < rowend;
       const int i = valid ? i_raw : rowend - 1;  // in-range row for the loads of idle lanes
@@ -1322,20 +1288,6 @@ __device__ __forceinline__ void round_block_nib(const GhDev& d, const int cur, c
       const uint32_t islot = (uint32_t)(i - d.row0);
       const uint32_t ow = islot * (TW / 2) + lbp;
       owu[u] = ow;
-      if constexpr (DMA) {
-        const int o = (u * RPW + sub) * (TW / 2) + (int)lbp;
-        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-        const u2 q2 = *reinterpret_cast<const u2*>(wb + o);
-        const u2 a2 = *reinterpret_cast<const u2*>(wb + 1024 + o);
-        qwu[u].v[0] = q2[0], qwu[u].v[1] = q2[1];
-        awu[u].v[0] = a2[0], awu[u].v[1] = a2[1];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const u2 g2 = *reinterpret_cast<const u2*>(wb + 2048 + q * 1024 + o);
-          pwu[u][q].v[0] = g2[0], pwu[u][q].v[1] = g2[1];
-        }
-        continue;
-      }
       // the age words are read once (no peer reads them): they stream past
       // the caches the plane lines live in; the own plane words are a line
       // the row's receivers gather too
@@ -1381,7 +1333,7 @@ __device__ __forceinline__ void round_block_nib(const GhDev& d, const int cur, c
       }
     }
 #pragma unroll
-    for (int u = 0; u < RSD; ++u) {
+    for (int u = 0; u < RS; ++u) {
       const int i = iu[u];
       const bool al = alu[u];
       uint32_t QO[W], AO[W], LW[W], A1[W], Bm = 0, Lz = 0;
@@ -2228,13 +2180,12 @@ __device__ __forceinline__ void round_block(const GhDev& d, const int cur, const
 // 96 VGPRs, as its block loop left to the compiler took 106 and at 6 waves
 // spilled 72 bytes per lane; the host's full-grid REMOVE launch is IN 7).
 template <int KB, int TW, int TPW, bool NT, bool STORM, int IN>
-__global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM && TW >= 32) ? 4 : IN == 6 ? 5 : IN == 7 ? GH_RMV_WAVES : (IN == 2 || IN == 4 || IN == 5) ? GH_NIB_WAVES : 1) void k_round(GhDev d, int cur, int dcur, GhRound p) {
+__global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM && TW >= 32) ? 4 : IN == 6 ? 5 : IN == 7 ? GH_RMV_WAVES : (IN == 2 || IN == 4) ? GH_NIB_WAVES : 1) void k_round(GhDev d, int cur, int dcur, GhRound p) {
   if (*d.mode != (int)STORM) return;
   if constexpr (!STORM) {
     int want = 0;
     if (d.a4[0])
       want = !gh_m8(d, cur) ? 3 : (KB == 4 && p.plane && d.pvalid[cur] && gh_m8(d, cur ^ 1)) ? (d.rowlay ? 4 : 2) : 1;
-    if (want == 2 && p.nib_dma && TW == 256 && GH_NIB_CPL == 16) want = 5;  // LDS-DMA staging (GH_NIB_DMA)
     // a REMOVE pending (|D_{r-1}| > 0): the instantiation that takes it on the
     // nibble path (GH_NIB_RMV=2: in every round, A/B)
     // (p.rmv_full: the host launched IN 6 in place of IN 2, so IN 6 must run
@@ -2243,9 +2194,9 @@ __global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM 
     if (want != (IN == 7 ? 6 : IN)) return;  // (IN 7: IN 6 on a full grid)
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    d.m8[4] = STORM ? 1 : (IN == 2 || IN == 4 || IN == 5 || IN == 6 || IN == 7) ? 3 : IN == 1 ? 2 : 0;
+    d.m8[4] = STORM ? 1 : (IN == 2 || IN == 4 || IN == 6 || IN == 7) ? 3 : IN == 1 ? 2 : 0;
     // launch_round's variant number of this launch (IN 3 is variant 0 of a tiered engine)
-    constexpr int LV = STORM ? 1 : (IN == 6 || IN == 7) ? 4 : (IN == 2 || IN == 4 || IN == 5) ? 3 : IN == 1 ? 2 : 0;
+    constexpr int LV = STORM ? 1 : (IN == 6 || IN == 7) ? 4 : (IN == 2 || IN == 4) ? 3 : IN == 1 ? 2 : 0;
     d.m8[6] = LV;  // (gh_debug_variant)
     if (d.vlog) d.vlog[p.vslot] = LV;
   }
@@ -2263,7 +2214,7 @@ __global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM 
       __syncthreads();  // LDS of this block before the next
     }
   } else if constexpr (IN == 2) {
-    round_block_nib<TW, NT, GH_NIB_CPL, false, false, false>(d, cur, dcur, p, blockIdx.x);  // one block per workgroup
+    round_block_nib<TW, NT, GH_NIB_CPL, false, false>(d, cur, dcur, p, blockIdx.x);  // one block per workgroup
   } else if constexpr (IN == 4) {
     round_block_nib<TW, NT, GH_NIB_CPL, true>(d, cur, dcur, p, blockIdx.x);
   } else if constexpr (IN == 7) {
@@ -2281,8 +2232,6 @@ __global__ __launch_bounds__(256, (STORM && TW >= 64) ? GH_STORM_WAVES : (STORM 
       round_block_nib<TW, NT, GH_NIB_CPL, false>(d, cur, dcur, p, b);
       __syncthreads();  // LDS of this block before the next
     }
-  } else if constexpr (IN == 5) {
-    if constexpr (TW == 256 && GH_NIB_CPL == 16) round_block_nib<TW, NT, 16, false, true>(d, cur, dcur, p, blockIdx.x);
   } else {
     // one block per workgroup (a loop here costs the lean variants 20+ VGPRs)
     round_block<KB, TW, TPW, NT, STORM, IN>(d, cur, dcur, p, blockIdx.x);
@@ -3672,8 +3621,6 @@ static bool launch_round_tpw(const GhDev& d, int cur, int dcur, const GhRound& p
         case 3:
           if (d.rowlay)
             GH_ROUND_NT(false, 4);  // row layout: ghost senders
-          else if (p.nib_dma && TW == 256)
-            GH_ROUND_NT(false, 5);  // LDS-DMA staging
           else
             GH_ROUND_NT(false, 2);
           return true;

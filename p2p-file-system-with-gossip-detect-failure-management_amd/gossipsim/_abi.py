@@ -43,9 +43,8 @@ GH_CTL_REMOVE, GH_CTL_LEAVE, GH_CTL_JOIN = 1, 2, 4
 GH_ENS_MAX_MEMBERS = 128
 # gh_debug_knobs: the enum GH_KNOB_* of the header, in its order (each the
 # environment variable GH_<NAME> that gh_create reads)
-KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP", "FORCE_SLOW",
-         "FORCE_STORM", "ROUND_NT", "ROUND_TPW", "SLOW_GRID", "NIB_RMV", "NIB_DMA", "GX_DIRECT", "ROUND_XMAP",
-         "TMODE", "PLANE", "C8", "TILE_W")
+KNOBS = ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "FORCE_SLOW", "FORCE_STORM", "ROUND_NT", "ROUND_TPW",
+         "SLOW_GRID", "NIB_RMV", "GX_DIRECT", "ROUND_XMAP", "TMODE", "PLANE", "C8", "TILE_W")
 
 
 class Config(C.Structure):

@@ -46,7 +46,7 @@ def test_struct_layouts(abi):
 
 def test_abi_version_and_defaults(abi):
     lib = abi.load()
-    assert lib.gh_abi_version() == 7
+    assert lib.gh_abi_version() == 8
     cfg = abi.Config()
     lib.gh_config_default(C.byref(cfg))
     # reference constants: PERIOD/COOLDOWN 5 s at 1 s rounds, 4 replicas, literal 4
@@ -62,7 +62,7 @@ def test_knob_names_match_header(abi):
     names = [x.split("=")[0].strip() for x in enum.split(",") if x.strip()]
     assert names[-1] == "GH_KNOB_COUNT"
     assert tuple(n[len("GH_KNOB_"):] for n in names[:-1]) == abi.KNOBS
-    for switch in ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC", "SIDE", "SIDE_ORDER", "JOIN_STAMP",
+    for switch in ("QUIRK_ROWS", "JOBS_FLAT", "RMV_FULL7", "DNW", "NREC",
                    "FORCE_SLOW", "FORCE_STORM", "ROUND_NT", "ROUND_TPW", "SLOW_GRID"):
         assert switch in abi.KNOBS
     out = (C.c_int32 * len(abi.KNOBS))()

@@ -181,7 +181,7 @@ def test_config_layout(abi):
     assert abi.EnsConfig.peer_mode.offset == 20 and abi.EnsConfig.detect_mode.offset == 24
     cfg = abi.EnsConfig(16, 2, 3, 4, 0)  # the five-field form is today's ensemble
     assert (cfg.peer_mode, cfg.detect_mode) == (abi.GH_PEER_PULL, abi.GH_DETECT_CANONICAL)
-    assert abi.load().gh_abi_version() == 7
+    assert abi.load().gh_abi_version() == 8
 
 
 @pytest.mark.parametrize("field,value", [("peer_mode", 2), ("peer_mode", -1), ("detect_mode", 2), ("detect_mode", -1)])

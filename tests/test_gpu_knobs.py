@@ -1,16 +1,15 @@
 """Parity of every A/B and diagnostic fallback against the oracle. The
-environment switches gh_create reads (GH_JOBS_FLAT, GH_QUIRK_ROWS, GH_SIDE,
+environment switches gh_create reads (GH_JOBS_FLAT, GH_QUIRK_ROWS, GH_DNW,
 ...; include/gossiphip.h gh_debug_knobs) select paths that DESIGN.md's
 measurements are taken against and that no default run reaches: the region
 form of the lane jobs, the two-sweep quirk pre-pass, IN 6 on a full grid, the
-nibble path without its move words or row records, the idle variants in line
-or on two side streams, the storm variant and the per-cell rule everywhere,
-another grid of the per-cell kernel, other tilings. Each case sets its switch before the engine is created,
+nibble path without its move words or row records, the storm variant and the
+per-cell rule everywhere, another grid of the per-cell kernel, other tilings.
+Each case sets its switch before the engine is created,
 asserts through knobs() that the engine runs with it, and then runs one
-workload bit-exact against the oracle, stats and tables every round: the
-crash wave of test_gpu_tier8.py::test_tier_lds_dma_staging (N=2,048, k=4,
-T_fail = T_cleanup = 16, 1% crash at round 8, one rejoin at round 30, 36
-rounds). Run on a MI355X: pytest -m gpu."""
+workload bit-exact against the oracle, stats and tables every round: a
+crash wave (N=2,048, k=4, T_fail = T_cleanup = 16, 1% crash at round 8, one
+rejoin at round 30, 36 rounds). Run on a MI355X: pytest -m gpu."""
 import pytest
 
 import scenarios as sc
@@ -71,15 +70,13 @@ def test_knobs_defaults(gs, monkeypatch):
         kn = eng.knobs()
     finally:
         eng.close()
-    assert kn == dict(GH_QUIRK_ROWS=1, GH_JOBS_FLAT=1, GH_RMV_FULL7=1, GH_DNW=1, GH_NREC=1, GH_SIDE=1,
-                      GH_SIDE_ORDER=0, GH_JOIN_STAMP=1, GH_FORCE_SLOW=0, GH_FORCE_STORM=0, GH_ROUND_NT=1,
-                      GH_ROUND_TPW=1, GH_SLOW_GRID=768, GH_NIB_RMV=1, GH_NIB_DMA=0, GH_GX_DIRECT=1, GH_ROUND_XMAP=1,
-                      GH_TMODE=1, GH_PLANE=1, GH_C8=1, GH_TILE_W=256), kn
+    assert kn == dict(GH_QUIRK_ROWS=1, GH_JOBS_FLAT=1, GH_RMV_FULL7=1, GH_DNW=1, GH_NREC=1, GH_FORCE_SLOW=0,
+                      GH_FORCE_STORM=0, GH_ROUND_NT=1, GH_ROUND_TPW=1, GH_SLOW_GRID=768, GH_NIB_RMV=1,
+                      GH_GX_DIRECT=1, GH_ROUND_XMAP=1, GH_TMODE=1, GH_PLANE=1, GH_C8=1, GH_TILE_W=256), kn
 
 
-ONE_ENGINE = [("GH_JOBS_FLAT", 0), ("GH_RMV_FULL7", 0), ("GH_DNW", 0), ("GH_NREC", 0), ("GH_SIDE", 0), ("GH_SIDE", 2),
-              ("GH_SIDE_ORDER", 1), ("GH_JOIN_STAMP", 0), ("GH_ROUND_NT", 1), ("GH_ROUND_NT", 0), ("GH_FORCE_SLOW", 1),
-              ("GH_FORCE_STORM", 1), ("GH_SLOW_GRID", 96)]
+ONE_ENGINE = [("GH_JOBS_FLAT", 0), ("GH_RMV_FULL7", 0), ("GH_DNW", 0), ("GH_NREC", 0), ("GH_ROUND_NT", 1),
+              ("GH_ROUND_NT", 0), ("GH_FORCE_SLOW", 1), ("GH_FORCE_STORM", 1), ("GH_SLOW_GRID", 96)]
 
 
 @pytest.mark.parametrize("knob,value", ONE_ENGINE, ids=[f"{k}={v}" for k, v in ONE_ENGINE])

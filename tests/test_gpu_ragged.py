@@ -240,15 +240,14 @@ def test_ragged_quirk(gs, oracle_mod, monkeypatch, n, quirk_rows, crash):
 
 # ---- 5. the switches that change tail code -------------------------------------------------------------
 
-KNOBS = [("GH_NIB_DMA", 1), ("GH_DNW", 0), ("GH_NREC", 0), ("GH_JOBS_FLAT", 0), ("GH_JOBS_FLAT", 1),
-         ("GH_ROUND_XMAP", 0), ("GH_ROUND_XMAP", 2), ("GH_NIB_RMV", 0), ("GH_NIB_RMV", 2), ("GH_RMV_FULL7", 0),
-         ("GH_RMV_FULL7", 1)]
+KNOBS = [("GH_DNW", 0), ("GH_NREC", 0), ("GH_JOBS_FLAT", 0), ("GH_JOBS_FLAT", 1), ("GH_ROUND_XMAP", 0),
+         ("GH_ROUND_XMAP", 2), ("GH_NIB_RMV", 0), ("GH_NIB_RMV", 2), ("GH_RMV_FULL7", 0), ("GH_RMV_FULL7", 1)]
 
 
 @pytest.mark.parametrize("knob,value", KNOBS, ids=[f"{k}={v}" for k, v in KNOBS])
 def test_ragged_knobs(gs, oracle_mod, monkeypatch, knob, value):
     """N = 263, k = 4, the wave, with one switch set and asserted through
-    knobs(): LDS-DMA staging of lines that are mostly padding, the moves
+    knobs(): the moves
     derived from the bases over padded columns, rows staged from the inboxes
     in a partial row block, region and flat dealing of the lane jobs, the
     tile maps when seven of eight tiles are padding, the REMOVE forms on 1/8

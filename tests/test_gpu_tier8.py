@@ -412,26 +412,10 @@ def test_tier_remove_on_nibble_path(gs, oracle_mod, monkeypatch, case):
     assert on_jobs * 4 <= off_jobs, (on_jobs, off_jobs, [(r, trace[r - 1][2], off[r - 1][2]) for r in tomb_rounds])
 
 
-@pytest.mark.parametrize("case", ["steady_crash", "remove_quirk"])
-def test_tier_lds_dma_staging(gs, oracle_mod, monkeypatch, case):
-    """The nibble path with its lines staged by LDS-DMA (GH_NIB_DMA=1,
-    round.hip round_block_nib DMA: buffer_load_dwordx4 ... lds, 8 rows per
-    wave step) at N=2,048, k=4, T_fail=16: a crash wave with its detection,
-    REMOVE and release rounds (canonical, then quirk detection), bit-exact
-    against the oracle every round, the nibble path in the healthy rounds."""
-    monkeypatch.setenv("GH_NIB_DMA", "1")
-    n = 2048
-    cfg = dict(fanout=4, seed=0x5EED0D10, t_fail=16, t_cleanup=16, detect_mode=1 if case == "remove_quirk" else 0)
-    crashed = sc.crash_ids(n, 0.01, 0x5EED0D11)
-    sched = {8: [(sc.CRASH, int(c)) for c in crashed], 30: [(sc.JOIN, int(crashed[0]))]}
-    trace, _ = remove_run(gs, oracle_mod, n, cfg, sched, 36)
-    assert sum(v == 3 for _, v, _ in trace) >= 30, trace
-    assert any(s["tombstoned"] for s, _, _ in trace)
-
-
 @pytest.mark.parametrize("env", [("GH_ROUND_XMAP", "2"), ("GH_NIB_RMV", "2")])
 def test_tier_nibble_variants(gs, oracle_mod, monkeypatch, env):
-    """Two nibble-path options on the crash wave of test_tier_lds_dma_staging,
+    """Two nibble-path options on a crash wave (N=2,048, k=4, T_fail =
+    T_cleanup = 16, 1% crash at round 8, one rejoin at round 30, 36 rounds),
     bit-exact against the oracle every round: GH_ROUND_XMAP=2 (odd rounds
     sweep the tiles from the other end, round.hip nib_region; the lane jobs
     walk the same regions) and GH_NIB_RMV=2 (the REMOVE-taking

@@ -11,7 +11,7 @@ everything else.
 Part A: the nibble path at 64- and 128-member tiles. With GH_PLANE=1 an engine
 keeps the 4-bit tier from tile_width 64 up (gossiphip.cpp c8), so 64 and 128
 run round_block_nib<64|128> -- 4 and 8 16-cell lanes per segment instead of 16,
-no LDS-DMA and no split-gather form, ld padded to 8 * TW -- in the healthy
+no split-gather form, ld padded to 8 * TW -- in the healthy
 rounds and as the REMOVE-taking form. test_gpu_ragged.py's crash wave, with
 victims on both sides of the first and the last tile boundary of that width
 (scenarios.width_victims), asserts which variant ran, lane jobs, tier

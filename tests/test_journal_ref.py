@@ -151,7 +151,7 @@ def test_journal_symbols_and_bindings(abi):
         assert len(bound[name]) == nargs, name
     assert (abi.GH_JOURNAL_OFF, abi.GH_JOURNAL_DETECT, abi.GH_JOURNAL_VIEWS) == (jr.OFF, jr.DETECT, jr.VIEWS)
     assert abi.GH_JOURNAL_BINS == jr.BINS
-    assert lib.gh_abi_version() == 7
+    assert lib.gh_abi_version() == 8
     import gossipsim
     assert gossipsim.Journal._fields == jr.FIELDS
     assert gossipsim.JOURNAL_ROUND_DTYPE == jr.ROUND_DTYPE
